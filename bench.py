@@ -1,8 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the LiDAR-vision fusion hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line with the headline figure (`value` fused tokens/s,
+`ms_per_step`); nothing else runs.  `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs).
+`--full` adds every secondary measurement and check described below to the same line.
 
 A "step" is ONE pass of the hot path (lidar_vision_vqa_amd.pipeline.FusionPipeline) over one batch of `--scenes` synthetic
 scenes per GPU (default 32): points and image-patch tokens are already resident in HBM when the timed region starts.
@@ -16,8 +20,8 @@ VQA-head workload 256 LiDAR x 576 image x 32 answer tokens), both with the stand
 
 `value` is measured in the precision mode `--precision` (default "mixed": bf16 MFMA tiles everywhere, plain bf16 operands on the
 262 144-key K/V stream, hi + lo bf16 operands elsewhere -- the fastest mode that meets the north-star 1e-3 tolerance, see
-`parity_vs_cpu`, which is measured for EVERY mode timed in this run against the CPU oracle on three scenes).  Rank 0 prints ONE JSON line
-with `roofline` = the cross-attention kernel at the metric's own shape "32k pts x 196 patches" (lvq_ca_fused at (1, 32768, 196, 768, 12):
+`parity_vs_cpu` of a `--full` run, which is measured for EVERY mode timed there against the CPU oracle on three scenes).  With `--full`,
+rank 0's line also holds `roofline` = the cross-attention kernel at the metric's own shape "32k pts x 196 patches" (lvq_ca_fused at (1, 32768, 196, 768, 12):
 SURVEY 8d's algorithmic FLOPs / HIP-event time of its launches on the launch stream), `roofline_attention` = the dominant kernel of the
 step (VATLiDAR's cross-attention over the BEV key stream; three readings of its FLOPs), `roofline_bev_kv`, every cross-attention row of
 SURVEY 8d, the HBM-bound voxelisers at cfg-3, the same workload on Dist-U scenes and at the reference's default depth, and `cpu_baseline`
@@ -240,6 +244,30 @@ class HeadStage:
         return out.loss, out.logits[:, -self.n_answer:]
 
 
+DUMP_BUDGET = 60 << 20      # bytes of array data one --dump-outputs writes (64 MB at most)
+DUMP_WHOLE = 1 << 20        # arrays up to this size are written whole
+
+
+def dump_outputs(arrays, out_dir):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy, floating ones as float32, integer ones as float64 (both exact for
+    what the path returns).  Arrays above DUMP_WHOLE share the rest of DUMP_BUDGET equally; each larger one keeps a sample of its rows
+    (vectors along the last axis): np.random.default_rng(0).choice(n_rows, k, replace=False), sorted -- the same rows in every run that
+    returns the same number of rows."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: (v.float() if v.is_floating_point() else v.double()).cpu().numpy() for k, v in arrays.items() if v is not None}
+    large = sorted(k for k, a in host.items() if a.nbytes > DUMP_WHOLE)
+    share = (DUMP_BUDGET - sum(a.nbytes for k, a in host.items() if k not in large)) // max(1, len(large))
+    for k in large:
+        a = host[k]
+        rows = a.reshape(-1, a.shape[-1]) if a.ndim > 1 else a.reshape(-1, 1)
+        n = share // rows[0].nbytes
+        if n < len(rows):
+            rows = rows[np.sort(np.random.default_rng(0).choice(len(rows), n, replace=False))]
+        host[k] = rows if a.ndim > 1 else rows[:, 0]
+    for k, a in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -248,9 +276,13 @@ def main():
     ap.add_argument("--scenes", type=int, default=32, help="scenes per GPU per step")
     ap.add_argument("--precision", default="mixed", choices=list(MODES))
     ap.add_argument("--workload", default="cfg2", choices=["cfg2", "cfg4", "cfg5"], help="BASELINE configs[1] (default, the metric's own), [3] or [4]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other modes, cross-attention rows, voxelisers, Dist-U)")
+    ap.add_argument("--full", action="store_true", help="add the rooflines, the secondary measurements and the CPU baseline / parity check to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the secondary measurements (other modes, cross-attention rows, voxelisers, Dist-U)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -312,13 +344,15 @@ def main():
             fused = fuse(lt, im)
             loss, logits = head(im, fused)
         D.reduce_head_step(loss, logits, red)     # one fused buffer [loss * S | S | answer-logit sums], one all-reduce
-        return fused
+        return dict(fused=fused, loss=loss, answer_logits=logits)
 
-    ops.EVENTS = {}                 # event recording is on during warm-up too (first-use costs stay out of the timed region)
+    # per-launch HIP events feed only the --full figures; when on, recording is on during warm-up too (first-use costs stay out of the
+    # timed region)
+    ops.EVENTS = {} if args.full else None
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    ops.EVENTS = {}
+    ops.EVENTS = {} if args.full else None
     # a full CPython cycle collection (~30 ms with torch's module graph alive) otherwise lands inside the timed steps every
     # dozen iterations and stalls the launch stream: collect now, keep the survivors out of later scans
     gc.collect()
@@ -327,8 +361,9 @@ def main():
     D.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last = step()                   # what a caller of the timed path receives (--dump-outputs)
     torch.cuda.synchronize()
     D.barrier()
     dt = time.perf_counter() - t0
@@ -341,6 +376,17 @@ def main():
         gc.enable()
         D.finalize()
         return
+    if args.dump_outputs:
+        arrays = {**last, "reduced": red}
+        # the voxel / pillar outputs are buffers of the voxelisers' capacity: rows >= scene_*_off[S] are unspecified
+        for off_key, keys in (("scene_voxel_off", ("voxel_features", "voxel_coords", "voxel_num_points")),
+                              ("scene_pillar_off", ("pillar_features", "pillar_coords"))):
+            if off_key in arrays:
+                m = int(arrays[off_key][-1])
+                arrays.update({k: arrays[k][:m] for k in keys})
+        dump_outputs(arrays, args.dump_outputs)
+        del arrays
+    del last
 
     prec = args.precision
     result = {
@@ -350,8 +396,13 @@ def main():
         "dtype": "bf16", "data": "synthetic",
         "config": {"workload": workload, "scenes_per_gpu_per_step": S, "fused_tokens_per_scene": tokens_per_scene,
                    "parallelism": f"scene-parallel x{world}" + (f" (REHEARSAL: {world} ranks on {ndev} device(s), gloo)" if rehearsal else ""),
-                   "precision_mode": prec + " (bf16 / fp16 MFMA tiles throughout; see parity_vs_cpu for the error of every mode)"},
+                   "precision_mode": prec + " (bf16 / fp16 MFMA tiles throughout; see parity_vs_cpu of a --full run for the error of every mode)"},
     }
+    if not args.full:
+        gc.enable()
+        print(json.dumps(result), flush=True)
+        D.finalize()
+        return
 
     # ---- `roofline`: the cross-attention kernel at the metric's own shape (B, Nq, Nkv, d, h) = (1, 32768, 196, 768, 12), SURVEY 8d row 1 ----
     d, h = 768, 12

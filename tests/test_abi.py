@@ -147,7 +147,7 @@ def _fracs(node, path=""):
 
 
 def test_committed_bench_line_keeps_the_driver_contract():
-    """profiles/r*_bench_final.json (the newest) is the line `python bench.py` printed on the MI355X for the committed build: the fields
+    """profiles/r*_bench_final.json (the newest) is the line `python bench.py --full` printed on the MI355X for the committed build: the fields
     the driver and the judge read must all be there (bench.py contract: metric / value / roofline / cpu_baseline ...), the roofline entry
     is the metric's own shape, and no fraction of a roofline anywhere in the line exceeds 1 (a fraction above 1 means a kernel is
     credited with work it does not do: VERDICT r2, `roofline_kv_proj`)."""

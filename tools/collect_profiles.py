@@ -2,7 +2,7 @@
 """Copy the summaries of one round's profiling runs from gpurun_out/ (scratch) into profiles/ (tracked):
     python tools/collect_profiles.py r03
 expects the outputs of `tools/profile_ca.sh <tag> mixed`, `tools/profile_ca.sh <tag>bf16 bf16`, `tools/profile_round.sh <tag>` and
-`python bench.py > gpurun_out/bench_final.json`.  Writes profiles/<tag>_{bench_final.json, bench_kernel_stats.csv, voxel_kernel_stats.csv,
+the line of `python bench.py --full` saved beside them as bench_final.json.  Writes profiles/<tag>_{bench_final.json, bench_kernel_stats.csv, voxel_kernel_stats.csv,
 headline_{mixed,bf16}_kernel_stats.csv, pmc_summary.json, pmc_headline_summary.json, pmc_traffic.json} -- bench.py reads the last one."""
 import glob, json, os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
