@@ -1296,15 +1296,20 @@ __global__ void __launch_bounds__(256) k_attn_combine_signed(AttnArgs a) {
     }
     const bool judge = live && signed_b && d0 == 0;
     if (judge && a.flags && !(l > 0.0625f * lt && l < 3.0e38f)) {
-        a.flags[bh] = 1;
-        if (a.stats && qi == 0) atomicAdd(&a.stats[1], 1);
+        // any row of (b, h) may flag it: the pair is counted by the row that sets the flag, once whichever row that is
+        if (a.stats) {
+            if (atomicExch(&a.flags[bh], 1) == 0) atomicAdd(&a.stats[1], 1);
+        } else {
+            a.flags[bh] = 1;
+        }
     }
     // per-launch half of the plain-stream guard (lvq_stream_guard is the per-model half): rows whose softmax mass sits mostly on the
     // scene's own (dirty) keys, which the per-model statistic has not seen -> a count and the largest l / l_table.  One atomic per row on
     // one address serialised 221 000 of them (0.8 ms); reading the address first was worse (1.2 ms).  So: reduce over the workgroup, one
     // atomic pair per workgroup into one of STAT_SLOTS lines, and the re-run's merge (above) folds the slots into stats.
     if (slots) {
-        float ratio = (judge && lt > 0.f) ? fminf(l / lt, 3.0e38f) : 0.f;
+        // clamped to [0, 3e38]: the max is taken on the bits, and a row flagged by the cancellation check can end with l < 0
+        float ratio = (judge && lt > 0.f) ? fminf(fmaxf(l / lt, 0.f), 3.0e38f) : 0.f;
         int over = (judge && lt > 0.f && l > 1.5f * lt) ? 1 : 0;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) {

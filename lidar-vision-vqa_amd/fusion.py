@@ -171,9 +171,10 @@ class VATBlock(_HipModule):
         return self._mlp(y)
 
     def forward_tokens_tiled(self, q2: torch.Tensor, x_rows: BF, kv: torch.Tensor, row_src: torch.Tensor, rows_dev: torch.Tensor, B: int, nq: int,
-                             n_tiles: int) -> torch.Tensor:
+                             n_tiles: int) -> Tuple[torch.Tensor, BF]:
         """Block over the tiled BEV key stream (csrc/bev_tiles.hip): K|V of the DIRTY rows from x_rows into kv[HW:], every other key
-        from the per-model table in kv[:HW].  Plain K / V / P; weights and the query side keep their lo parts in the mixed mode."""
+        from the per-model table in kv[:HW].  Plain K / V / P; weights and the query side keep their lo parts in the mixed mode.
+        -> (block output, the cross-attention's Q projection BF [B*nq, d]: what the stream guard audits)."""
         d, h = self.d_model, self.n_heads
         dh = d // h
         hw = n_tiles * 64
@@ -184,7 +185,7 @@ class VATBlock(_HipModule):
         _, qp = ops.linear(qn, self._w(self.ca.in_proj_weight), self.ca.in_proj_bias, out_bf=True, w_rows=(0, d), tag="ca_q_proj")
         o = ops.attention_tiled(qp, kv, row_src, batch=B, n_heads=h, nq=nq, n_tiles=n_tiles, dh=dh, scale=1.0 / math.sqrt(dh), tag="ca_attn")
         y, _ = ops.linear(o, self._w(self.ca.out_proj.weight), self.ca.out_proj.bias, residual=q2, out_f32=True, tag="ca_out_proj")
-        return self._mlp(y)
+        return self._mlp(y), qp
 
     def _mlp(self, q2: torch.Tensor) -> torch.Tensor:
         split = self._split()
@@ -560,9 +561,10 @@ class VATLiDAR(_HipModule):
         return int(a), int(b), float(torch.tensor([c], dtype=torch.int32).view(torch.float32))
 
     def _audit_scene(self, qp_hi: torch.Tensor, table: torch.Tensor, src: torch.Tensor, scene: int, n_keys: int, k16: bool = False) -> torch.Tensor:
-        """Per-scene half of the guard: the statistic of lvq_stream_guard on the ACTUAL key stream of one scene (its computed rows and the
-        table rows of its clean cells, gathered through row_src) -> 0-d device tensor max(g).  ~4 ms at 262 144 keys: run on a sample of
-        the scenes (audit_every) or on all of them (strict_parity)."""
+        """Per-scene half of the guard: the statistic of lvq_stream_guard on the ACTUAL key stream of one scene for one block (qp_hi [nq, d]:
+        that block's queries for this scene; its K|V buffer's computed rows and the table rows of the clean cells, gathered through row_src)
+        -> 0-d device tensor max(g).  ~4 ms at 262 144 keys: run on a sample of the scenes (audit_every) or on all of them (first call of a
+        weights version, strict_parity)."""
         blk = self.blocks[0]
         d = blk.d_model
         rows = src.view(-1, n_keys)[scene].long()
@@ -570,6 +572,14 @@ class VATLiDAR(_HipModule):
         if k16:                                                           # "mixed16": the K half holds IEEE fp16 bit patterns
             k_scene = k_scene.view(torch.float16).to(torch.bfloat16)
         return ops.stream_guard(qp_hi, k_scene, blk.n_heads, 1.0 / math.sqrt(d // blk.n_heads)).max()
+
+    def _audit(self, qps: List[torch.Tensor], kvs: List[torch.Tensor], src: torch.Tensor, scenes, n_keys: int, k16: bool) -> torch.Tensor:
+        """_audit_scene over the given scenes and EVERY block: qps[li] = block li's Q projection (hi part), [nq, d] when shared by all scenes
+        (block 0 of the signed stream) else [batch * nq, d] -> 0-d device tensor, the largest statistic."""
+        nq = self.n_queries
+        g = [self._audit_scene(q if q.shape[0] == nq else q[b * nq:(b + 1) * nq], kvs[li], src, b, n_keys, k16 and li == 0)
+             for li, q in enumerate(qps) for b in scenes]
+        return torch.stack(g).max()
 
     def _guard_poll(self) -> bool:
         """True when an audit whose read-back has completed exceeded the threshold (no synchronisation: the answer lags by a call or two)."""
@@ -627,12 +637,18 @@ class VATLiDAR(_HipModule):
         if guarded:
             # The plain-bf16 key stream is parity-true only while the softmax mass is spread over many keys.  Two checks of the
             # same statistic (lvq_stream_guard), both structural: (1) once per weights version, the model's own queries over the table keys
-            # (the empty scene: 70-100 % of every scene's keys); (2) an audit of the ACTUAL key stream -- every audit_every-th call one scene
-            # (results are read back without synchronisation and trip the module a call or two later), or every scene of every call with
-            # the call redone on the spot (strict_parity).  A model / scene stream that fails runs hi + lo operands everywhere instead.
-            tripped = getattr(self, "_guard_tripped", None) == self._guard_version()
+            # (the empty scene: 70-100 % of every scene's keys); (2) an audit of the ACTUAL key stream of every block -- every scene of the
+            # first call of a weights version, with the call redone on the spot if it fails (and so of every call with strict_parity); then
+            # every audit_every-th call one scene (results are read back without synchronisation and trip the module a call or two later).
+            # A model / scene stream that fails runs hi + lo operands everywhere instead.
+            ver = self._guard_version()
+            if getattr(self, "_guard_ver", None) != ver:         # new weights: audited afresh, nothing read back under the old ones applies
+                object.__setattr__(self, "_guard_ver", ver)
+                object.__setattr__(self, "_guard_calls", 0)
+                object.__setattr__(self, "_guard_pending", None)
+            tripped = getattr(self, "_guard_tripped", None) == ver
             if not tripped and self._guard_poll():
-                object.__setattr__(self, "_guard_tripped", self._guard_version())
+                object.__setattr__(self, "_guard_tripped", ver)
                 tripped = True
             if tripped or self.stream_guard(C, H, W, dev) > self.STREAM_GUARD_MAX:
                 return self._forward_pillars_hilo(pillar_features, coords_bzyx, n_live, batch, H, W, all_tiles_live)
@@ -656,6 +672,7 @@ class VATLiDAR(_HipModule):
         live, dirty, src, counts = ops.bev_tiles(idx, batch, H, W, dev, H * W, force_all=all_tiles_live)
         x_live = None if fused else self._tile_tokens(feat, idx, live, dirty, counts, batch * nt * 64, batch, H, W)
         q2 = None if signed else self._queries(batch)
+        qps = []                                               # every block's Q projection (hi part): the guard's audit
         for li, (blk, table) in enumerate(zip(self.blocks, kvs)):
             blk.precision = self.precision
             if fused:
@@ -666,19 +683,21 @@ class VATLiDAR(_HipModule):
                     object.__setattr__(self, "_guard_stats", torch.zeros(4, dtype=torch.int32, device=dev))
                 q2 = blk.forward_tokens_tiled_signed(q2_1, qp, totals, x_live, table, src, counts[2:], batch, self.n_queries, nt, k_fp16=k16,
                                                      stats=self._guard_stats)
+                qps.append(qp[0])
             else:
-                q2 = blk.forward_tokens_tiled(q2, x_live, table, src, counts[2:], batch, self.n_queries, nt)
+                q2, qp_l = blk.forward_tokens_tiled(q2, x_live, table, src, counts[2:], batch, self.n_queries, nt)
+                qps.append(qp_l[0])
         self._last_tile_counts = counts                       # device tensor (live pieces, their rows, dirty rows): read by bench / tests only
-        if guarded and qp is not None:
-            calls = getattr(self, "_guard_calls", 0)
+        if guarded:
+            calls = self._guard_calls
             object.__setattr__(self, "_guard_calls", calls + 1)
-            if self.strict_parity:
-                g = torch.stack([self._audit_scene(qp[0], kvs[0], src, b, H * W, k16) for b in range(batch)]).max()
+            if self.strict_parity or calls == 0:
+                g = self._audit(qps, kvs, src, range(batch), H * W, k16)
                 if float(g) > self.STREAM_GUARD_MAX:             # synchronises: this very call is redone with hi + lo operands
                     object.__setattr__(self, "_guard_tripped", self._guard_version())
                     return self._forward_pillars_hilo(pillar_features, coords_bzyx, n_live, batch, H, W, all_tiles_live)
             elif self.audit_every and calls % self.audit_every == 0:
-                self._guard_submit(self._audit_scene(qp[0], kvs[0], src, (calls // self.audit_every) % batch, H * W, k16))
+                self._guard_submit(self._audit(qps, kvs, src, [(calls // self.audit_every) % batch], H * W, k16))
         return _post_head(self, q2, self.final_ln, self.post).view(batch, self.n_queries, self.d_model)
 
     def _guard_version(self):

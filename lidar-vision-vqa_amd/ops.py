@@ -465,10 +465,11 @@ def attention_tiled_signed(q: BF, kv: torch.Tensor, row_src: torch.Tensor, pair_
 
 
 def stream_guard(q_hi: torch.Tensor, k_rows: torch.Tensor, n_heads: int, scale: float) -> torch.Tensor:
-    """Per-model half of the plain-stream guard (include/lvq.h: lvq_stream_guard): q_hi [nq, n_heads * 64] bf16, k_rows [nkv, >= n_heads * 64]
-    bf16 (row stride = k_rows.stride(0)) -> g [n_heads, nq] fp32, g = (1 + max |score|) / sqrt(N_eff) per (head, query)."""
-    F.require_cuda(q_hi)
-    assert q_hi.dtype == torch.bfloat16 and k_rows.dtype == torch.bfloat16 and k_rows.stride(1) == 1 and k_rows.is_cuda
+    """Per-model half of the plain-stream guard (include/lvq.h: lvq_stream_guard): q_hi [nq, >= n_heads * 64] bf16, k_rows [nkv, >= n_heads * 64]
+    bf16 (row strides = q_hi.stride(0), k_rows.stride(0): column slices of a wider projection are taken as they are) -> g [n_heads, nq] fp32,
+    g = (1 + max |score|) / sqrt(N_eff) per (head, query)."""
+    F.require_cuda(q_hi[:1], k_rows[:1])                              # device only: rows may be strided, elements within a row may not
+    assert q_hi.dtype == torch.bfloat16 and k_rows.dtype == torch.bfloat16 and q_hi.stride(1) == 1 and k_rows.stride(1) == 1
     nq, nkv = q_hi.shape[0], k_rows.shape[0]
     dev = q_hi.device
     L = F.lib()

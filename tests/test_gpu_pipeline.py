@@ -103,7 +103,6 @@ def test_pipeline_mixed_mode_meets_the_bar_at_full_size():
     pts, off, patches, pts_np, patches_np = P.synthetic_batch(cfg, 1, 1100, DEV)
     out = pipe(pts, off, patches)
     sd = lambda m: {k: v.detach().cpu() for k, v in m.state_dict().items()}
-    torch.set_num_threads(__import__("os").cpu_count() or 1)
     ref = PO.run(cfg, pts_np, patches_np, sd(pipe.pillar_vfe), sd(pipe.vat_lidar), sd(pipe.fuse), do_3d=False)
     err = (out["fused"].cpu() - ref["fused"]).abs().max().item()
     err_l = (out["lidar_tokens"].cpu() - ref["lidar_tokens"]).abs().max().item()

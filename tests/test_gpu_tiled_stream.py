@@ -305,6 +305,91 @@ def test_attention_tiled_signed_falls_back_when_unusable(kind):
     assert torch.equal(oh, ref[0]) and torch.equal(ol, ref[1])
 
 
+def _guard_case(B, H, nq, n_tiles, fr, seed):
+    """Operands for the per-launch guard counters: heads h % 4 == 0 take the `cancel` construction of
+    test_attention_tiled_signed_falls_back_when_unusable (table keys x6, computed keys x0.01, the table keys of cells clean in some batch
+    x0.002: the signed row sum ends far below 1/16 of the table's), heads h % 4 == 1 computed keys x3 (the softmax mass moves onto the
+    scene's own keys: row sum > 1.5x the table's), the other heads as drawn.  Query row 0 is zero: its row sum equals the table's exactly,
+    so it never flags -- the (batch, head) pairs are flagged by other rows only."""
+    hw = n_tiles * 64
+    kv, src, is_dirty = _row_case(B, H, n_tiles, fr, seed)
+    t32 = kv.float()
+    tab = t32[:hw]
+    clean_somewhere = (~is_dirty).any(0).to(t32.device)
+    for h in range(H):
+        c = slice(64 * h, 64 * h + 64)
+        if h % 4 == 0:
+            tab[:, c] *= 6.0
+            t32[hw:, c] *= 0.01
+            tab[clean_somewhere, c] *= 0.002
+        elif h % 4 == 1:
+            t32[hw:, c] *= 3.0
+    q = torch.randn(nq, H * 64, generator=torch.Generator().manual_seed(seed + 1))
+    q[0] = 0.0
+    return t32.to(torch.bfloat16), src, is_dirty, q
+
+
+def _guard_ratios_fp64(qh, ql, kv, src, signed, H, n_tiles):
+    """Host fp64: ratio[b, h, i] = sum_e exp(s(q_i, K[src[b, e]])) / sum_e exp(s(q_i, K[e])) over the n_tiles * 64 key slots, with the operands
+    the kernel sees (q = hi + lo, K in bf16, s = q . k / 8) -> [len(signed), H, nq]."""
+    hw = n_tiles * 64
+    q = qh.cpu().double() + ql.cpu().double()
+    k = kv[:, :H * 64].cpu().double()
+    dirty = [torch.nonzero(src[b] != torch.arange(hw, dtype=src.dtype)).view(-1) for b in signed]     # the dirty slots of each batch
+    out = torch.empty(len(signed), H, q.shape[0], dtype=torch.float64)
+    for h in range(H):
+        c = slice(64 * h, 64 * h + 64)
+        s_tab = (q[:, c] @ k[:hw, c].t()) * 0.125
+        l_tab = torch.logsumexp(s_tab, 1)
+        for j, (b, e) in enumerate(zip(signed, dirty)):
+            s_b = s_tab.clone()
+            s_b[:, e] = (q[:, c] @ k[src[b, e].long(), c].t()) * 0.125
+            out[j, h] = torch.exp(torch.logsumexp(s_b, 1) - l_tab)
+    return out
+
+
+@pytest.mark.parametrize("B,H,nq,n_tiles,fr", [(3, 4, 576, 128, [0.3, 0.7, 0.2]), (2, 12, 576, 256, [0.6, 0.25])])
+def test_attention_tiled_signed_guard_counters_vs_fp64(B, H, nq, n_tiles, fr):
+    """The per-launch half of the plain-stream guard (lvq_attention_bf16_tiled_signed's `stats`, include/lvq.h) against a host fp64
+    restatement: [0] = judged rows (signed batches) whose row sum exceeds 1.5x the table's, [1] = (batch, head) pairs of signed batches
+    that some row flags for the re-run (row sum < 1/16 of the table's) -- counted once each, whichever row flags it --, [2] = the largest
+    row sum / table row sum.  A batch over 50 % dirty runs its full list and is not judged.  The words accumulate over calls, and asking
+    for them does not change the result."""
+    o = ops()
+    hw = n_tiles * 64
+    kv, src, is_dirty, q = _guard_case(B, H, nq, n_tiles, fr, 41)
+    kv = kv.to(DEV)
+    qb = o.cast(q.to(DEV), True)
+    srcd = src.to(DEV).contiguous()
+    pair_src, pair_info = o.bev_scene_pairs(srcd, B, n_tiles, hw)
+    tot = o.attention_stream_totals(qb, kv[:hw], n_heads=H, nq=nq, nkv=hw, dh=64, scale=1.0 / 8.0)
+
+    def run(stats):
+        return o.attention_tiled_signed(qb, kv, srcd, pair_src, pair_info, tot, batch=B, n_heads=H, nq=nq, n_tiles=n_tiles, dh=64,
+                                        scale=1.0 / 8.0, shared_q=True, stats=stats)
+
+    s = torch.zeros(4, dtype=torch.int32, device=DEV)
+    oh, ol = run(s)
+    first = s.cpu().clone()
+    signed = [b for b in range(B) if int(pair_info[b, 1])]
+    assert signed == [b for b in range(B) if fr[b] < 0.5]
+    r = _guard_ratios_fp64(qb[0], qb[1], kv, src, signed, H, n_tiles)
+    assert bool((r[:, :, 0] == 1.0).all())                                       # the zero query: row sum == table row sum
+    for t in (1.5, 1.0 / 16):                                                      # no row near a threshold: the counts are exact
+        assert float(((r - t).abs() / t).min()) > 0.01, t
+    want = (int((r > 1.5).sum()), int((r < 1.0 / 16).any(2).sum()), float(r.max()))
+    assert want[0] > 0 and want[1] > 0
+    got_max = float(first[2:3].view(torch.float32))
+    assert int(first[0]) == want[0], ("rows over 1.5x", int(first[0]), want[0])
+    assert int(first[1]) == want[1], ("re-run pairs", int(first[1]), want[1])
+    assert abs(got_max - want[2]) <= 1e-3 * want[2], ("largest ratio", got_max, want[2])
+    again = run(s)
+    assert s.cpu().tolist() == [2 * int(first[0]), 2 * int(first[1]), int(first[2]), int(first[3])]
+    plain = run(None)
+    for x in (again, plain):
+        assert torch.equal(x[0], oh) and torch.equal(x[1], ol)
+
+
 @pytest.mark.parametrize("B,H,nq,n_tiles,fr,qsplit", [(2, 2, 120, 64, 0.35, True), (3, 4, 576, 128, [0.4, 0.9, 0.0], True), (2, 12, 576, 256, [0.2, 0.45], True),
                                                       (1, 2, 120, 67, 0.3, True), (2, 2, 240, 72, 0.3, False)])
 def test_pipelined_stream_is_bit_identical(B, H, nq, n_tiles, fr, qsplit, tune):
