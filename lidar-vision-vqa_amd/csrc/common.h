@@ -82,3 +82,11 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 }
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// rotary frequency of pair e of a dh-wide head as transformers' Qwen2 rotary embedding computes it in fp32:
+// inv_freq = 1 / theta ** (arange(0, dh, 2) / dh), the power rounded once (evaluated in fp64).  powf(theta, -2e/dh) differs from it
+// by an ulp in about one pair in six, and the angle pos * inv_freq then by up to 2e-3 rad at position 32000.
+__device__ __forceinline__ float rope_inv_freq(float theta, int e, int dh) {
+    const float ex = (float)(2 * e) / (float)dh;
+    return 1.0f / (float)pow((double)theta, (double)ex);
+}

@@ -9,7 +9,7 @@
 namespace {
 
 // rotary embedding at position pos applied in place to the q and k heads of the packed rows (the arithmetic of k_rope in
-// elementwise.hip: angle = pos * theta^(-2e/dh), rotate-half pairs), the rotated keys and the values appended to the caches:
+// elementwise.hip: angle = pos * rope_inv_freq(theta, e, dh), rotate-half pairs), the rotated keys and the values appended to the caches:
 // rope + rope + append were three launches of a one-token step
 __global__ void __launch_bounds__(256) k_rope_cache(uint16_t *__restrict__ xh, uint16_t *__restrict__ xl, int batch, int n_heads, int n_kv_heads,
                                                     int dh, int pos, int lmax, float theta, uint16_t *__restrict__ kc, uint16_t *__restrict__ kcl,
@@ -23,7 +23,7 @@ __global__ void __launch_bounds__(256) k_rope_cache(uint16_t *__restrict__ xh, u
     const int b = i / per_row, j = i - b * per_row;
     if (j < nrope) {
         const int hd = j / half, e = j - hd * half;
-        const float inv = powf(theta, -2.0f * (float)e / (float)dh);
+        const float inv = rope_inv_freq(theta, e, dh);
         float sn, cs;
         sincosf((float)pos * inv, &sn, &cs);
         const int64_t o1 = (int64_t)b * ld + (int64_t)hd * dh + e, o2 = o1 + half;

@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(256) k_scale_add_rows(const float *__restrict_
     out[i] = v;
 }
 
-// rotate-half rotary embedding (transformers Qwen2): x[..., :h] , x[..., h:] with angle pos * theta^(-2i/dh)
+// rotate-half rotary embedding (transformers Qwen2): x[..., :h] , x[..., h:] with angle pos * inv_freq[i] (rope_inv_freq)
 __global__ void __launch_bounds__(256) k_rope(uint16_t *__restrict__ xh, uint16_t *__restrict__ xl, int64_t rows, int seq_len,
                                               int n_heads, int dh, int64_t ld, float theta, int pos0) {
     const int half = dh >> 1;
@@ -349,7 +349,7 @@ __global__ void __launch_bounds__(256) k_rope(uint16_t *__restrict__ xh, uint16_
     const int hd = (int)((i / half) % n_heads);
     const int64_t row = i / ((int64_t)half * n_heads);
     const int pos = pos0 + (int)(row % seq_len);
-    const float inv = powf(theta, -2.0f * (float)e / (float)dh);
+    const float inv = rope_inv_freq(theta, e, dh);
     float sn, cs;
     sincosf((float)pos * inv, &sn, &cs);
     const int64_t o1 = row * ld + (int64_t)hd * dh + e, o2 = o1 + half;
@@ -364,9 +364,10 @@ __global__ void __launch_bounds__(256) k_rope(uint16_t *__restrict__ xh, uint16_
 // argmax over wide rows (vocabulary 151 936): one workgroup per row streamed 600 KB through one CU (191 us).  Now a row is split
 // into chunks of 8192; every workgroup reduces its chunk and publishes (orderable value bits << 32 | ~index) with one 64-bit
 // atomicMax into out[row] (zeroed first), a second tiny kernel unpacks the index.  Larger value wins; equal values: smaller index.
+// -0.0 is packed as +0.0: the two compare equal, as in torch.argmax ([-0.0, 0.0] -> 0).
 constexpr int ARGMAX_CHUNK = 8192;
 __device__ __forceinline__ unsigned long long argmax_pack(float v, int i) {
-    uint32_t u = __float_as_uint(v);
+    uint32_t u = v == 0.f ? 0u : __float_as_uint(v);
     u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                 // monotone float -> uint
     return ((unsigned long long)u << 32) | (uint32_t)(0xffffffffu - (uint32_t)i);
 }

@@ -167,13 +167,17 @@ def test_gemm_live_rows_device_count():
             g32 = o.to_f32(got)
             if rows:
                 assert float((g32[:rows] - ref[:rows]).abs().max()) <= 2.0 ** -7 * float(ref.abs().max()), (rows, a_split, w_split)
-            # rows past the last whole 256-row tile of the live count are never written
+            # rows past the last whole 256-row tile of the live count are never written (`out=` takes plain operands only)
             up = (rows + 255) // 256 * 256
-            if up < cap:
-                got[0][up:].fill_(canary)
-                again = o.linear_live_rows(ab, wb, bias, rd, (64, 64 + n))
-                del again
-            del canary
+            if not a_split:
+                out = torch.full((cap, n), canary, dtype=torch.bfloat16, device=DEV)
+                keep = out.clone()
+                same = o.linear_live_rows(ab, wb, bias, rd, (64, 64 + n), out=out)
+                assert same[0].data_ptr() == out.data_ptr() and same[1] is None
+                if rows:
+                    assert float((out[:rows].float() - ref[:rows]).abs().max()) <= 2.0 ** -7 * float(ref.abs().max()), (rows, w_split)
+                    assert torch.equal(out[:rows], got[0][:rows]), (rows, w_split)
+                assert torch.equal(out[up:].view(torch.int16), keep[up:].view(torch.int16)), (rows, w_split)     # rows = 0: nothing written
 
 
 def _row_case(B, H, n_tiles, dirty_frac, seed, k_new_scale=1.0, k_tab_scale=1.0, shuffle=True):
