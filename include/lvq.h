@@ -518,6 +518,36 @@ int lvq_qwen2_decode_step(const lvq_qwen2_layer *layers, int n_layers, float *x,
                           int inter, int pos, int lmax, float rms_eps, float rope_theta, int precision, void *ws, size_t ws_bytes,
                           lvq_stream_t stream);
 
+/* ---- Ragged decode (csrc/decode_ragged.hip): a batch whose sequences stand at different positions ----------------------------
+ * Decode attention of inference_engine.py:283-296 -> transformers generate with a KV cache, for a batch of prompts of different
+ * length: ONE query token per sequence over the first kv_len[b] rows of its cache,
+ *   O[b,h,:] = softmax_j( Q[b,h,:].K[b,j,h/g,:] * scale ) V[b,j,h/g,:],   j < kv_len[b],   g = n_heads / n_kv_heads <= 16.
+ *   q rows [batch, n_heads * dh], caches [batch, lmax, n_kv_heads * dh], o [batch, n_heads * dh] (bf16 hi, optional lo), addressed with
+ *   the strides of lvq_attention_bf16 (ldq / ldo are accepted and unused: there is one query row); operand strides are multiples
+ *   of 8 elements and operand pointers 16-byte aligned.  kv_len [batch] int32 on the DEVICE, read by the kernels only (no host read,
+ *   no synchronisation); values are clamped to 0 .. lmax, a length of 0 writes zeros, cache rows at and beyond kv_len[b] are
+ *   never loaded.  q_lo != NULL selects hi + lo operands (then k_cache_lo and v_cache_lo are required), the bf16x3 mode of
+ *   lvq_attention_bf16; otherwise plain bf16.  dh multiple of 16, <= 128; scale > 0.
+ * The query heads of one KV head are the columns of one MFMA tile, so a cache row is loaded once per KV head.  The work of sequence b
+ * (fixed-length key chunks, merged in ascending order) depends on kv_len[b] alone: its output bits do not depend on the batch. */
+size_t lvq_attention_decode_ragged_workspace_bytes(int batch, int n_heads, int n_kv_heads, int lmax, int dh, int precision);
+int lvq_attention_decode_ragged(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *k_cache, const lvq_bf16 *k_cache_lo,
+                                const lvq_bf16 *v_cache, const lvq_bf16 *v_cache_lo, const int32_t *kv_len, int batch, int n_heads,
+                                int n_kv_heads, int lmax, int dh, int64_t q_bstride, int64_t ldq, int64_t q_hstride, int64_t k_bstride,
+                                int64_t ldk, int64_t k_hstride, int64_t v_bstride, int64_t ldv, int64_t v_hstride, int64_t o_bstride,
+                                int64_t ldo, int64_t o_hstride, float scale, lvq_bf16 *o, lvq_bf16 *o_lo, void *ws, size_t ws_bytes,
+                                lvq_stream_t stream);
+/* lvq_qwen2_decode_step for a ragged batch (inference_engine.py:283-296 -> transformers generate with a KV cache, prompts of different length):
+ * the new token of sequence b sits at position pos0[b] + t and attends keys 0 .. pos0[b] + t.  pos0 [batch] int32 on the DEVICE, never
+ * written: a decode loop passes the prompt lengths once and t = 0, 1, ...  0 <= t < lmax is checked on the host; a sequence with
+ * pos0[b] + t >= lmax is clamped on the device to position lmax - 1 (it keeps overwriting its last cache row -- its output is then
+ * meaningless, but nothing is written outside its cache).  Same projections, norms and SwiGLU calls as lvq_qwen2_decode_step; at
+ * equal positions the appended cache rows have equal bits.  Head geometries of lvq_attention_decode_ragged only (else LVQ_EINVAL). */
+size_t lvq_qwen2_decode_ragged_workspace_bytes(int batch, int d, int n_heads, int n_kv_heads, int inter, int lmax, int precision);
+int lvq_qwen2_decode_step_ragged(const lvq_qwen2_layer *layers, int n_layers, float *x, int batch, int d, int n_heads, int n_kv_heads,
+                                 int inter, const int32_t *pos0, int t, int lmax, float rms_eps, float rope_theta, int precision,
+                                 void *ws, size_t ws_bytes, lvq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,7 @@ Two deliberate differences from the reference:
 """
 from __future__ import annotations
 
+import inspect
 from dataclasses import dataclass
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple, Union
@@ -158,8 +159,76 @@ class InferenceEngine:
         """The reference's signature and defaults (inference_engine.py:229-240); `generator` seeds the sampled path."""
         return self.answer(question, bev, sample_token, Decoding(max_new_tokens, temperature, top_p, top_k, do_sample, num_beams), generator)
 
-    def generate_batch(self, questions: List[str], bevs: List[BevInput], sample_tokens: Optional[List[str]] = None,
+    @torch.no_grad()
+    def answer_batch(self, questions: Sequence[str], bevs: Sequence[BevInput], sample_tokens: Optional[Sequence[Optional[str]]],
+                     decoding: Decoding, generator=None) -> List[str]:
+        """`answer` for several (question, bev[, sample_token]) triples with ONE `base_model.generate` call: the LiDAR prefix runs once on
+        the stacked BEVs (once per shape group when the canvases differ), the vision prefix per sample, every prompt is embedded with
+        `build_inputs_embeds`, the prompts are right-padded to a common length and decoded as a ragged batch
+        (`generate(..., prompt_lengths=)`: head.StandInHead).  A `base_model.generate` without a `prompt_lengths` parameter (a
+        transformers model object) gets the per-question loop."""
+        n = len(questions)
+        tokens = list(sample_tokens) if sample_tokens is not None else [None] * n
+        if n == 0:
+            return []
+        if "prompt_lengths" not in inspect.signature(self.base_model.generate).parameters:
+            return [self.answer(q, b, t, decoding, generator) for q, b, t in zip(questions, bevs, tokens)]
+        loaded = [self._load_bev(b) for b in bevs]
+        loaded = [(b if b.ndim == 4 else b[None]).to(self.device) for b in loaded]
+        lidar: List[Optional[torch.Tensor]] = [None] * n
+        groups: Dict[tuple, List[int]] = {}
+        for i, b in enumerate(loaded):
+            if b.shape[0] != 1:
+                raise F.LvqError("answer_batch: one BEV canvas ([C, H, W] or [1, C, H, W]) per question")
+            groups.setdefault(tuple(b.shape), []).append(i)
+        for idx in groups.values():
+            rows = self.process_lidar(torch.cat([loaded[i] for i in idx], dim=0))
+            for k, i in enumerate(idx):
+                lidar[i] = rows[k:k + 1]
+        embs = []
+        for i, (q, t) in enumerate(zip(questions, tokens)):
+            vision = None
+            if self.use_vision and t is not None:
+                try:
+                    vision = self.process_vision(t)
+                except Exception as err:       # LiDAR-only answer instead of no answer, as in `_prefixes`
+                    print(f"[engine] vision prefix unavailable for {t!r} ({err}); answering from LiDAR only")
+            prompt = self.format_prompt(q, include_vision=vision is not None)
+            embs.append(self.build_inputs_embeds(prompt, lidar[i], vision)[0])
+        lens = torch.tensor([e.shape[1] for e in embs], dtype=torch.int32, device=self.device)
+        width = max(e.shape[1] for e in embs)
+        batch = torch.zeros((n, width, embs[0].shape[2]), dtype=embs[0].dtype, device=self.device)
+        for i, e in enumerate(embs):
+            batch[i, :e.shape[1]] = e[0]
+        mask = (torch.arange(width, device=self.device)[None, :] < lens[:, None]).long()
+        extra = {"generator": generator} if generator is not None else {}
+        new_ids = self.base_model.generate(inputs_embeds=batch, attention_mask=mask, prompt_lengths=lens, **decoding.kwargs(self.tokenizer), **extra)
+        eos = self.tokenizer.eos_token_id
+        out = []
+        for row in new_ids.tolist():
+            if eos is not None and eos in row:             # what the sequence's own loop returns: it stops with its EOS
+                row = row[:row.index(eos) + 1]
+            out.append(self.tokenizer.decode(row, skip_special_tokens=True).strip())
+        return out
+
+    def generate_batch(self, questions: List[str], bevs: List[BevInput], sample_tokens: Optional[List[str]] = None, batch_size: int = 1,
                        **generation_kwargs) -> List[str]:
-        """One answer per (question, bev[, sample_token]) triple, in order (inference_engine.py:306-336)."""
+        """One answer per (question, bev[, sample_token]) triple, in order (inference_engine.py:306-336).  The questions are answered in
+        groups of `batch_size`: a group of one is a `generate` call (the default: the reference's loop), a larger group is one
+        `answer_batch` call -- one LiDAR pass and one ragged decode loop for the group.  `batch_size` is the caller's memory / latency
+        choice; greedy answers do not depend on it beyond the precision mode's rounding."""
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
         tokens = sample_tokens if sample_tokens is not None else [None] * len(questions)
-        return [self.generate(q, b, t, **generation_kwargs) for q, b, t in zip(questions, bevs, tokens)]
+        triples = list(zip(questions, bevs, tokens))
+        out: List[str] = []
+        for i in range(0, len(triples), batch_size):
+            group = triples[i:i + batch_size]
+            if len(group) == 1:
+                out.append(self.generate(*group[0], **generation_kwargs))
+            else:
+                kw = dict(generation_kwargs)
+                generator = kw.pop("generator", None)
+                qs, bs, ts = zip(*group)
+                out += self.answer_batch(qs, bs, ts, Decoding(**kw), generator)
+        return out

@@ -220,11 +220,30 @@ class StandInHead(_HipModule):
                                      p(wd[0]), p(wd[1]), p(kh), p(kl), p(vh), p(vl))
         return arr, keep
 
+    def _ragged_prompts(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor], prompt_lengths: torch.Tensor):
+        """Checks of a ragged generate call.  Returns (inputs_embeds with the padding rows zeroed, prompt lengths as int32 [B] on the
+        device = pos0 of lvq_qwen2_decode_step_ragged)."""
+        B, L, _ = inputs_embeds.shape
+        dev = inputs_embeds.device
+        if not isinstance(prompt_lengths, torch.Tensor) or prompt_lengths.is_floating_point() or prompt_lengths.dtype == torch.bool \
+                or tuple(prompt_lengths.shape) != (B,):
+            raise F.LvqError(f"StandInHead.generate: prompt_lengths must be an integer tensor of shape [{B}]")
+        lens = prompt_lengths.to(device=dev, dtype=torch.long)
+        if not bool(((lens >= 1) & (lens <= L)).all()):
+            raise F.LvqError(f"StandInHead.generate: prompt_lengths must lie in 1 .. {L}")
+        real = torch.arange(L, device=dev)[None, :] < lens[:, None]                     # [B, L]: right-padded layout
+        if attention_mask is not None:
+            if tuple(attention_mask.shape) != (B, L) or not bool(((attention_mask.to(dev) != 0) == real).all()):
+                raise F.LvqError("StandInHead.generate: with prompt_lengths the attention_mask must be None or the right-padded mask of "
+                                 "those lengths (left padding is not supported)")
+        emb = torch.where(real[:, :, None], inputs_embeds, torch.zeros((), dtype=inputs_embeds.dtype, device=dev))
+        return emb, lens.to(torch.int32).contiguous()
+
     @torch.no_grad()
     def generate(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_new_tokens: int = 64,
                  do_sample: bool = False, num_beams: int = 1, pad_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, output_scores: bool = False, temperature: float = 1.0, top_k: Optional[int] = 50,
-                 top_p: float = 1.0, generator: Optional[torch.Generator] = None, **unused):
+                 top_p: float = 1.0, generator: Optional[torch.Generator] = None, prompt_lengths: Optional[torch.Tensor] = None, **unused):
         """`base_model.generate(inputs_embeds=, attention_mask=, max_new_tokens=, temperature=, top_p=, top_k=, do_sample=,
         num_beams=1, pad_token_id=, eos_token_id=)` as inference_engine.py:283-296 calls it, with a per-layer KV cache.
         do_sample=False: greedy (first maximum).  do_sample=True (the reference's default, temperature 0.7 / top_k 50 / top_p 0.9):
@@ -232,18 +251,28 @@ class StandInHead(_HipModule):
         come from torch's RNG (`generator` or torch.manual_seed), so runs are reproducible but -- like any two sampling
         implementations -- not stream-identical to transformers' multinomial.  Returns the NEW token ids [B, n] (what transformers
         returns when only inputs_embeds is given); with output_scores=True also the per-step raw logits [B, n, V].  Beam search
-        is not built."""
+        is not built.
+
+        prompt_lengths = None: every row of inputs_embeds is a whole prompt (all-ones attention_mask).  prompt_lengths = int tensor
+        [B] with 1 <= prompt_lengths[b] <= L: a RAGGED batch -- row b holds its prompt in positions 0 .. len_b-1, the rows behind it
+        are padding (zeroed here; attention_mask is None or the matching right-padded mask).  The prefill is the same causal call
+        over L rows (padding lies behind the real rows, so causality keeps it out of them), the first logits come from row len_b-1,
+        and every decode step is one lvq_qwen2_decode_step_ragged call with sequence b at position len_b + t, so each sequence sees
+        what it would see alone.  Ragged calls exist in the native step only: with LVQ_DECODE_PYTHON set they raise LvqError."""
         self._guard(inputs_embeds)
         if num_beams != 1:
             raise F.LvqError("StandInHead.generate: beam search is not implemented (num_beams must be 1)")
         if do_sample and not (temperature > 0.0 and 0.0 < top_p <= 1.0):
             raise ValueError("temperature must be > 0 and top_p in (0, 1]")
-        if attention_mask is not None and not bool((attention_mask == 1).all()):
+        ragged = prompt_lengths is not None
+        if not ragged and attention_mask is not None and not bool((attention_mask == 1).all()):
             raise F.LvqError("StandInHead.generate expects an all-ones attention_mask (the reference builds exactly that)")
         c = self.cfg
         B, L, d = inputs_embeds.shape
         dkv = self.dh * c["n_kv_heads"]
         dev = inputs_embeds.device
+        if ragged:
+            inputs_embeds, pos0 = self._ragged_prompts(inputs_embeds, attention_mask, prompt_lengths)
         lmax = L + max_new_tokens
         split = self._split()
         mk = lambda: (torch.empty((B, lmax, dkv), dtype=torch.bfloat16, device=dev),
@@ -251,14 +280,20 @@ class StandInHead(_HipModule):
         cache = [(mk(), mk()) for _ in self.model.layers]
         x = self._layers(_f32(inputs_embeds).view(B * L, d), B, L, 0, cache)          # prefill
         native = not os.environ.get("LVQ_DECODE_PYTHON")       # decode steps: one native call per token (csrc/decoder.hip)
+        if ragged and not native:
+            raise F.LvqError("StandInHead.generate: a ragged batch (prompt_lengths) has no Python-driven decode loop; unset LVQ_DECODE_PYTHON")
         if native:
             lib = F.lib()
             layers_arr, keep = self._native_layers(cache)
             prec = 3 if split else 1
-            nbytes = lib.lvq_qwen2_decode_workspace_bytes(F.cint(B), F.cint(d), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]),
-                                                          F.cint(c["inter"]), F.cint(lmax), F.cint(prec))
+            ws_query = lib.lvq_qwen2_decode_ragged_workspace_bytes if ragged else lib.lvq_qwen2_decode_workspace_bytes
+            nbytes = ws_query(F.cint(B), F.cint(d), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(lmax), F.cint(prec))
             step_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        step_logits = self._logits(x.view(B, L, d)[:, -1].contiguous())                 # [B, V]
+        if ragged:                                             # last real row of every sequence
+            last = x.view(B, L, d)[torch.arange(B, device=dev), pos0.long() - 1].contiguous()
+        else:
+            last = x.view(B, L, d)[:, -1].contiguous()
+        step_logits = self._logits(last)                                                # [B, V]
         pad = 0 if pad_token_id is None else int(pad_token_id)
         unfinished = torch.ones(B, dtype=torch.bool, device=dev)
         ids, scores = [], []
@@ -276,7 +311,13 @@ class StandInHead(_HipModule):
             if t + 1 == max_new_tokens:
                 break
             x = self.embed(nxt).float().contiguous()
-            if native:
+            if ragged:                                         # sequence b at position pos0[b] + t (csrc/decode_ragged.hip)
+                rc = lib.lvq_qwen2_decode_step_ragged(layers_arr, F.cint(len(self.model.layers)), F.ptr(x), F.cint(B), F.cint(d),
+                                                      F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.ptr(pos0), F.cint(t),
+                                                      F.cint(lmax), F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec),
+                                                      F.ptr(step_ws), F.csize(step_ws.numel()), F.stream_ptr(dev))
+                F.check(rc, "lvq_qwen2_decode_step_ragged")
+            elif native:
                 rc = lib.lvq_qwen2_decode_step(layers_arr, F.cint(len(self.model.layers)), F.ptr(x), F.cint(B), F.cint(d),
                                                F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(L + t), F.cint(lmax),
                                                F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec), F.ptr(step_ws),

@@ -173,6 +173,37 @@ def attention(q: BF, k: BF, v: BF, *, batch: int, n_heads: int, n_kv_heads: int,
     return oh, ol
 
 
+def attention_decode_ragged(q: BF, k_cache: BF, v_cache: BF, kv_len: torch.Tensor, *, batch: int, n_heads: int, n_kv_heads: int, lmax: int,
+                            dh: int, q_strides, k_strides, v_strides, scale: float) -> BF:
+    """One query token per sequence over the first kv_len[b] rows of its K / V cache (include/lvq.h: lvq_attention_decode_ragged).
+    q / k_cache / v_cache: BF views, *_strides = (batch, row, head) in elements as in `attention`; kv_len: int32 [batch] on the
+    device.  Returns BF [batch, n_heads*dh] (lo part when q is split)."""
+    qh, ql = q
+    dev = qh.device
+    if kv_len.dtype != torch.int32 or kv_len.device != dev or kv_len.numel() != batch or not kv_len.is_contiguous():
+        raise F.LvqError("attention_decode_ragged: kv_len must be a contiguous int32 tensor [batch] on the operands' device")
+    split = ql is not None
+    oh, ol = _bf_empty((batch, n_heads * dh), dev, split)
+    L = F.lib()
+    nbytes = L.lvq_attention_decode_ragged_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(n_kv_heads), F.cint(lmax), F.cint(dh),
+                                                           F.cint(3 if split else 1))
+    key = (dev.index, "attn_ragged")
+    ws = _ATT_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        _ATT_WS[key] = ws
+    d = n_heads * dh
+    rc = L.lvq_attention_decode_ragged(
+        F.ptr(qh), F.ptr(ql), F.ptr(k_cache[0]), F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(kv_len), F.cint(batch),
+        F.cint(n_heads), F.cint(n_kv_heads), F.cint(lmax), F.cint(dh),
+        F.i64(q_strides[0]), F.i64(q_strides[1]), F.i64(q_strides[2]),
+        F.i64(k_strides[0]), F.i64(k_strides[1]), F.i64(k_strides[2]),
+        F.i64(v_strides[0]), F.i64(v_strides[1]), F.i64(v_strides[2]),
+        F.i64(d), F.i64(d), F.i64(dh), F.cfloat(scale), F.ptr(oh), F.ptr(ol), F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+    F.check(rc, f"lvq_attention_decode_ragged (B={batch}, H={n_heads}, Hkv={n_kv_heads}, lmax={lmax}, dh={dh})")
+    return oh, ol
+
+
 def ca_fused_ok(batch: int, nq: int, nkv: int, d: int, n_heads: int) -> bool:
     """Shapes of the fused short-K/V cross-attention kernel (include/lvq.h: lvq_ca_fused_ok)."""
     return bool(F.lib().lvq_ca_fused_ok(F.cint(batch), F.cint(nq), F.cint(nkv), F.cint(d), F.cint(n_heads)))
