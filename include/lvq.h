@@ -548,6 +548,54 @@ int lvq_qwen2_decode_step_ragged(const lvq_qwen2_layer *layers, int n_layers, fl
                                  int inter, const int32_t *pos0, int t, int lmax, float rms_eps, float rope_theta, int precision,
                                  void *ws, size_t ws_bytes, lvq_stream_t stream);
 
+/* ---- Shared-prefix decode (csrc/decode_shared.hip): many sequences behind one cached prefix ------------------------------------------
+ * The reference's batch mode (infer.py:225-314) answers every question of a scene with its own inference_engine.py:283-296 call, which
+ * prefills the same vision / LiDAR prefix again.  Here sequence b continues prefix g = prefix_index[b]: its history is rows
+ * 0 .. plen[g]-1 of the prefix caches [n_prefix, pmax, n_kv_heads * dh] followed by the rows of its own caches [batch, lown, n_kv_heads * dh].
+ * Nothing is copied: a key at global position p is read from the prefix cache when p < plen[g], else from own row p - plen[g].
+ * Sequence b brings qn[b] query rows (q [batch, lq, n_heads * dh]; rows r >= qn[b] are padding and get a zero output) behind own0[b] own
+ * rows that are already cached; the keys / values of the query rows themselves are own rows own0[b] .. own0[b] + qn[b] - 1 (the caller
+ * has appended them).  Query row r stands at global position plen[g] + own0[b] + r and sees every key up to and including that one:
+ *   O[b,r,h,:] = softmax_j( Q[b,r,h,:].K[j,h/g,:] * scale ) V[j,h/g,:],   j <= plen[g] + own0[b] + r.
+ * One entry point serves the question prefill (own0 = 0, qn = question length) and a decode step (lq = 1, qn = 1).
+ *   prefix_index, own0, qn [batch] and plen [n_prefix]: int32 on the DEVICE, read by the kernels only (no host read, no
+ *   synchronisation), clamped to what the buffers hold; rows behind a length are never loaded.  Strides as lvq_attention_bf16 (the
+ *   prefix and the own caches share row and head strides and have their own batch strides); operand strides are multiples of 8
+ *   elements, operand pointers 16-byte aligned.  q_lo != NULL selects hi + lo operands (then every cache needs its lo part).
+ *   dh multiple of 16, <= 128; n_heads / n_kv_heads <= 16; scale > 0.
+ * Keys are cut into the fixed 128-key chunks of lvq_attention_decode_ragged at GLOBAL positions and the columns of the MFMA tile are
+ * (query row, query head) pairs of one KV head: the work of a sequence depends on its own lengths alone (its output bits do not
+ * depend on the batch), and with lq = 1 the output is bit-identical to lvq_attention_decode_ragged on a cache that holds the prefix
+ * rows and the own rows one behind the other. */
+size_t lvq_attention_extend_shared_workspace_bytes(int batch, int lq, int n_heads, int n_kv_heads, int pmax, int lown, int dh, int precision);
+int lvq_attention_extend_shared(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *pk_cache, const lvq_bf16 *pk_cache_lo,
+                                const lvq_bf16 *pv_cache, const lvq_bf16 *pv_cache_lo, const lvq_bf16 *k_cache, const lvq_bf16 *k_cache_lo,
+                                const lvq_bf16 *v_cache, const lvq_bf16 *v_cache_lo, const int32_t *prefix_index, const int32_t *plen,
+                                const int32_t *own0, const int32_t *qn, int batch, int lq, int n_heads, int n_kv_heads, int n_prefix,
+                                int pmax, int lown, int dh, int64_t q_bstride, int64_t ldq, int64_t q_hstride, int64_t pk_bstride,
+                                int64_t k_bstride, int64_t ldk, int64_t k_hstride, int64_t pv_bstride, int64_t v_bstride, int64_t ldv,
+                                int64_t v_hstride, int64_t o_bstride, int64_t ldo, int64_t o_hstride, float scale, lvq_bf16 *o,
+                                lvq_bf16 *o_lo, void *ws, size_t ws_bytes, lvq_stream_t stream);
+/* per-layer prefix caches [n_prefix, pmax, dkv] (post-rotary keys), read-only */
+typedef struct {
+    const lvq_bf16 *k, *k_lo, *v, *v_lo;
+} lvq_qwen2_prefix;
+/* The layer loop of lvq_qwen2_decode_step_ragged (inference_engine.py:283-296 -> transformers generate with a KV cache) on batch * lq rows
+ * that continue shared prefixes: x [batch, lq, d] fp32 in / out; row r < qn[b] of sequence b is rotated at position
+ * plen[prefix_index[b]] + own0[b] + t + r, appended to row own0[b] + t + r of the own caches of `layers` [batch, lown, dkv] and attends
+ * as lvq_attention_extend_shared describes; rows r >= qn[b] are padding (nothing appended, output meaningless).  prefix: HOST array of
+ * n_layers structs.  own0 is never written: a decode loop passes the question lengths once and t = 0, 1, ... with lq = 1 and qn = 1;
+ * the question prefill passes own0 = 0, t = 0.  0 <= t < lown is checked on the host; a row past the own cache
+ * (own0[b] + t + r >= lown) is clamped on the device to row lown - 1, which several rows may then write at once: nothing is written
+ * outside the cache, but the results of such a sequence are UNDEFINED -- size lown >= max_b(own0[b] + qn[b]) + the tokens to come.  With lq = 1 and batch <= 8 the projections are the calls of lvq_qwen2_decode_step_ragged: output and
+ * appended rows are bit-identical to that step on concatenated caches. */
+size_t lvq_qwen2_extend_shared_workspace_bytes(int batch, int lq, int d, int n_heads, int n_kv_heads, int inter, int pmax, int lown,
+                                               int precision);
+int lvq_qwen2_extend_shared(const lvq_qwen2_layer *layers, const lvq_qwen2_prefix *prefix, int n_layers, float *x, int batch, int lq, int d,
+                            int n_heads, int n_kv_heads, int inter, const int32_t *prefix_index, const int32_t *plen, int n_prefix, int pmax,
+                            const int32_t *own0, const int32_t *qn, int t, int lown, float rms_eps, float rope_theta, int precision, void *ws,
+                            size_t ws_bytes, lvq_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,14 +16,8 @@
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) short bf16x8;
-typedef __attribute__((ext_vector_type(4))) short bf16x4;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
-
-constexpr int RKVB = 64;        // keys per MFMA tile
-constexpr int RCHUNK = 128;     // keys per work unit: FIXED (see above); a multiple of RKVB
-static_assert(RCHUNK % RKVB == 0, "a chunk is whole key tiles");
+constexpr int RKVB = LVQ_RKVB;
+constexpr int RCHUNK = LVQ_RCHUNK;      // keys per work unit: FIXED (see above)
 
 struct RaggedArgs {
     const uint16_t *q, *ql, *k, *kl, *v, *vl;
@@ -35,18 +29,6 @@ struct RaggedArgs {
     float *part;                // [B][H][nchunk][DHP + 4] fp32: unnormalised O (DHP) | m (log2 domain) | l | pad
 };
 
-// two fp32 -> packed bf16 pair (v_cvt_pk_bf16_f32: round-to-nearest-even)
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-    bf16x2_t p = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(uint32_t, p);
-}
-// max over the four lane groups g = lane >> 4 that hold different keys of the same query
-__device__ __forceinline__ float max_over_groups(float x) {
-    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    x = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
 __device__ __forceinline__ int clamp_len(int len, int lmax) { return len < 0 ? 0 : (len > lmax ? lmax : len); }
 
 // DHP = padded head dim (64 or 128), NS = operand parts (1: plain bf16, 2: hi + lo -> three MFMA passes, the bf16x3 mode)

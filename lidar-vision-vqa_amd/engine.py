@@ -71,6 +71,33 @@ def _splice(ids: torch.Tensor, text: torch.Tensor, inserts: Sequence[Tuple[int, 
     return torch.cat([t for t in out if t.shape[1] > 0], dim=1)
 
 
+class Scene:
+    """One scene whose modal prefix -- everything `format_prompt` puts in front of the text, up to and including `<lidar_end>` -- has gone
+    through the encoders and the head's prefill once (`InferenceEngine.open_scene`).  `ask` answers questions about it from that cache."""
+
+    def __init__(self, engine: "InferenceEngine", lidar: torch.Tensor, vision: Optional[torch.Tensor], rows: torch.Tensor, prefix):
+        self.engine, self.lidar, self.vision, self.rows, self.prefix = engine, lidar, vision, rows, prefix
+
+    @property
+    def n_rows(self) -> int:
+        """P: embedding rows of the cached prefix"""
+        return self.rows.shape[1]
+
+    def question_rows(self, question: str) -> torch.Tensor:
+        """The embedding rows [1, n, d] of this question's prompt BEHIND the scene's prefix.  The whole prompt is built as `answer` builds
+        it and its first P rows must be the scene's, bit for bit (the end marker is a special token, so P is a token boundary)."""
+        eng = self.engine
+        emb = eng.build_inputs_embeds(eng.format_prompt(question, include_vision=self.vision is not None), self.lidar, self.vision)[0]
+        P = self.n_rows
+        if emb.shape[1] <= P or not torch.equal(emb[:, :P], self.rows):
+            raise F.LvqError("Scene.ask: the prompt of this question does not start with the scene's cached prefix rows")
+        return emb[:, P:]
+
+    def ask(self, questions: Sequence[str], **generation_kwargs) -> List[str]:
+        """One answer per question, in order, from ONE ragged decode loop behind the cached prefix (`generation_kwargs` as `generate`)."""
+        return self.engine._ask_scenes([(self, q) for q in questions], generation_kwargs)
+
+
 class InferenceEngine:
     def __init__(self, models: Dict):
         need = ("tokenizer", "base_model", "vat_lidar", "config", "device", "d_model")
@@ -203,6 +230,9 @@ class InferenceEngine:
         mask = (torch.arange(width, device=self.device)[None, :] < lens[:, None]).long()
         extra = {"generator": generator} if generator is not None else {}
         new_ids = self.base_model.generate(inputs_embeds=batch, attention_mask=mask, prompt_lengths=lens, **decoding.kwargs(self.tokenizer), **extra)
+        return self._decode_rows(new_ids)
+
+    def _decode_rows(self, new_ids: torch.Tensor) -> List[str]:
         eos = self.tokenizer.eos_token_id
         out = []
         for row in new_ids.tolist():
@@ -211,16 +241,113 @@ class InferenceEngine:
             out.append(self.tokenizer.decode(row, skip_special_tokens=True).strip())
         return out
 
+    # ---- many questions about one scene: the modal prefix is encoded and prefilled once ----
+    @torch.no_grad()
+    def open_scene(self, bev: BevInput, sample_token: Optional[str] = None) -> Scene:
+        """`process_lidar` (and `process_vision`) once, then the head's prefill of the prompt rows up to and including `<lidar_end>`
+        (`base_model.prefill_prefix`: head.StandInHead).  The result answers any number of questions with `Scene.ask`."""
+        if not callable(getattr(self.base_model, "prefill_prefix", None)):
+            raise F.LvqError("open_scene: base_model has no prefill_prefix (head.StandInHead has); use generate / generate_batch")
+        lidar, vision = self._prefixes(bev, sample_token)
+        if lidar.shape[0] != 1:
+            raise F.LvqError("open_scene: one BEV canvas ([C, H, W] or [1, C, H, W]) per scene")
+        # format_prompt puts the modal blocks first; the rows behind <lidar_end> of this question-less prompt are dropped
+        prompt = self.format_prompt("", include_vision=vision is not None)
+        ids = self.tokenizer(prompt, return_tensors="pt", add_special_tokens=False)["input_ids"][0]
+        end = torch.nonzero(ids == self.lidar_end_id).flatten()
+        if end.numel() == 0:
+            raise F.LvqError("open_scene: the prompt carries no <lidar_end> marker")
+        n_tail = ids.numel() - 1 - int(end[0])                 # text tokens behind the marker
+        emb = self.build_inputs_embeds(prompt, lidar, vision)[0]
+        rows = emb[:, :emb.shape[1] - n_tail].contiguous()
+        return Scene(self, lidar, vision, rows, self.base_model.prefill_prefix(rows))
+
+    @torch.no_grad()
+    def _ask_scenes(self, pairs: Sequence[Tuple[Scene, str]], generation_kwargs: dict) -> List[str]:
+        """[(scene, question)] -> answers in order, with ONE `base_model.generate` call.  The scenes' caches must be one PrefixCache or
+        single-prefix caches of equal width; several of them are stacked (byte movement) so that `prefix_index` selects among them."""
+        if not pairs:
+            return []
+        kw = dict(generation_kwargs)
+        generator = kw.pop("generator", None)
+        decoding = Decoding(**kw)
+        scenes: List[Scene] = []
+        for sc, _ in pairs:
+            if not any(sc is s for s in scenes):
+                scenes.append(sc)
+        prefix = scenes[0].prefix if len(scenes) == 1 else self._stack_prefixes([s.prefix for s in scenes])
+        index = [next(i for i, s in enumerate(scenes) if s is sc) for sc, _ in pairs]
+        embs = [sc.question_rows(q) for sc, q in pairs]
+        n = len(embs)
+        lens = torch.tensor([e.shape[1] for e in embs], dtype=torch.int32, device=self.device)
+        width = max(e.shape[1] for e in embs)
+        batch = torch.zeros((n, width, embs[0].shape[2]), dtype=embs[0].dtype, device=self.device)
+        for i, e in enumerate(embs):
+            batch[i, :e.shape[1]] = e[0]
+        mask = (torch.arange(width, device=self.device)[None, :] < lens[:, None]).long()
+        extra = {"generator": generator} if generator is not None else {}
+        new_ids = self.base_model.generate(inputs_embeds=batch, attention_mask=mask, prompt_lengths=lens, prefix=prefix,
+                                           prefix_index=torch.tensor(index, dtype=torch.int32, device=self.device),
+                                           **decoding.kwargs(self.tokenizer), **extra)
+        return self._decode_rows(new_ids)
+
+    @staticmethod
+    def _stack_prefixes(prefixes):
+        """Single-scene PrefixCaches -> one cache [G, pmax, dkv] per layer for a call that mixes scenes (row copies; no arithmetic)."""
+        from .head import PrefixCache
+        first = prefixes[0]
+        pmax = max(p.pmax for p in prefixes)
+        if any(p.mode != first.mode or p.version != first.version or p.owner() is not first.owner() for p in prefixes):
+            raise F.LvqError("scenes of one call must come from the same head, weights and precision mode")
+
+        def stack(parts):
+            if parts[0] is None:
+                return None
+            out = torch.zeros((sum(t.shape[0] for t in parts), pmax, parts[0].shape[2]), dtype=parts[0].dtype, device=parts[0].device)
+            g = 0
+            for t in parts:
+                out[g:g + t.shape[0], :t.shape[1]] = t
+                g += t.shape[0]
+            return out
+        layers = []
+        for i in range(len(first.layers)):
+            layers.append(tuple(tuple(stack([p.layers[i][kv][part] for p in prefixes]) for part in (0, 1)) for kv in (0, 1)))
+        return PrefixCache(layers, torch.cat([p.plen for p in prefixes]), [n for p in prefixes for n in p.lengths], pmax, first.mode,
+                           first.version, first.owner)
+
     def generate_batch(self, questions: List[str], bevs: List[BevInput], sample_tokens: Optional[List[str]] = None, batch_size: int = 1,
-                       **generation_kwargs) -> List[str]:
+                       share_scenes: bool = False, **generation_kwargs) -> List[str]:
         """One answer per (question, bev[, sample_token]) triple, in order (inference_engine.py:306-336).  The questions are answered in
         groups of `batch_size`: a group of one is a `generate` call (the default: the reference's loop), a larger group is one
         `answer_batch` call -- one LiDAR pass and one ragged decode loop for the group.  `batch_size` is the caller's memory / latency
-        choice; greedy answers do not depend on it beyond the precision mode's rounding."""
+        choice; greedy answers do not depend on it beyond the precision mode's rounding.
+
+        share_scenes=True: triples with the same `sample_token` and the same BEV (the same path string or the same object; contents are
+        not hashed) are questions about ONE scene.  Every scene is opened once (`open_scene`: one LiDAR pass, one prefill of its modal
+        prefix) when its first question comes up and released behind its last one, and groups of `batch_size` questions -- of one scene or of several -- decode in one loop behind the cached prefixes
+        (`generate(prefix=, prefix_index=)`).  Answers come back in input order.  A `base_model` whose `generate` has no `prefix`
+        parameter gets the path above."""
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")
         tokens = sample_tokens if sample_tokens is not None else [None] * len(questions)
         triples = list(zip(questions, bevs, tokens))
+        if share_scenes and "prefix" in inspect.signature(self.base_model.generate).parameters:
+            # a scene is opened when its first question comes up and dropped behind its last one: a QA file with thousands of sample
+            # tokens holds the prefix caches of the scenes of ONE group at a time (plus those that straddle a group boundary)
+            keys = [(t, str(b) if isinstance(b, (str, Path)) else id(b)) for _, b, t in triples]
+            last = {k: i for i, k in enumerate(keys)}
+            scenes: Dict[tuple, Scene] = {}
+            shared: List[str] = []
+            for i in range(0, len(triples), batch_size):
+                pairs = []
+                for (q, b, t), k in zip(triples[i:i + batch_size], keys[i:i + batch_size]):
+                    if k not in scenes:
+                        scenes[k] = self.open_scene(b, t)
+                    pairs.append((scenes[k], q))
+                shared += self._ask_scenes(pairs, generation_kwargs)
+                for k in [k for k in scenes if last[k] < i + batch_size]:
+                    del scenes[k]
+            return shared
         out: List[str] = []
         for i in range(0, len(triples), batch_size):
             group = triples[i:i + batch_size]

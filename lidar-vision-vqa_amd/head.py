@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import math
 import os
+import weakref
 from typing import Optional, Tuple
 
 import torch
@@ -97,6 +98,24 @@ class _Qwen2LayerPtrs(_ct.Structure):
     """include/lvq.h: lvq_qwen2_layer (device pointers of one decoder layer)."""
     _fields_ = [(n, _ct.c_void_p) for n in ("ln1", "ln2", "wqkv", "wqkv_lo", "bqkv", "wo", "wo_lo", "wgu", "wgu_lo", "wdown", "wdown_lo",
                                              "k_cache", "k_cache_lo", "v_cache", "v_cache_lo")]
+
+
+class _Qwen2PrefixPtrs(_ct.Structure):
+    """include/lvq.h: lvq_qwen2_prefix (device pointers of one layer's shared prefix caches)."""
+    _fields_ = [(n, _ct.c_void_p) for n in ("k", "k_lo", "v", "v_lo")]
+
+
+class PrefixCache:
+    """What `StandInHead.prefill_prefix` keeps of G prefixes for `generate(prefix=)`: per layer the K / V rows [G, pmax, dkv] (hi, and lo in
+    the bf16x3 mode), the lengths `plen` (int32 [G] on the device; `lengths` the same numbers on the host), and what the rows were
+    computed with -- the head, its precision mode and the version of its weights.  Read-only: any number of generate calls may use it."""
+
+    def __init__(self, layers, plen, lengths, pmax, mode, version, owner):
+        self.layers, self.plen, self.lengths, self.pmax, self.mode, self.version, self.owner = layers, plen, lengths, pmax, mode, version, owner
+
+    @property
+    def n_prefix(self) -> int:
+        return len(self.lengths)
 
 
 class HeadOutput:
@@ -239,11 +258,73 @@ class StandInHead(_HipModule):
         emb = torch.where(real[:, :, None], inputs_embeds, torch.zeros((), dtype=inputs_embeds.dtype, device=dev))
         return emb, lens.to(torch.int32).contiguous()
 
+    def _weights_version(self):
+        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+
+    @torch.no_grad()
+    def prefill_prefix(self, inputs_embeds: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> PrefixCache:
+        """The decoder stack on G prompt prefixes [G, P, d] (one causal prefill, the call `generate` makes for a prompt), kept as a
+        `PrefixCache` that later `generate(prefix=)` calls continue.  lengths = None: every prefix has P rows; an int tensor [G] with
+        1 <= lengths[g] <= P: prefix g is rows 0 .. lengths[g]-1, the rows behind it are padding (zeroed here; causality keeps them out of
+        the real rows, and no later call reads their K / V)."""
+        self._guard(inputs_embeds)
+        G, P, d = inputs_embeds.shape
+        dev = inputs_embeds.device
+        if lengths is None:
+            lengths = torch.full((G,), P, dtype=torch.int32, device=dev)
+        emb, plen = self._ragged_prompts(inputs_embeds, None, lengths)
+        dkv = self.dh * self.cfg["n_kv_heads"]
+        split = self._split()
+        mk = lambda: (torch.empty((G, P, dkv), dtype=torch.bfloat16, device=dev),
+                      torch.empty((G, P, dkv), dtype=torch.bfloat16, device=dev) if split else None)
+        cache = [(mk(), mk()) for _ in self.model.layers]
+        self._layers(_f32(emb).view(G * P, d), G, P, 0, cache)
+        return PrefixCache(cache, plen, [int(n) for n in plen.tolist()], P, self._mode(), self._weights_version(), weakref.ref(self))
+
+    def _shared_prompts(self, inputs_embeds, attention_mask, prompt_lengths, prefix, prefix_index):
+        """Checks of a generate call that continues a PrefixCache.  Returns (rows behind the prefix with the padding zeroed, their counts as
+        int32 [B], prefix_index as int32 [B])."""
+        B, L, _ = inputs_embeds.shape
+        dev = inputs_embeds.device
+        if not isinstance(prefix, PrefixCache) or prefix.owner() is not self:
+            raise F.LvqError("StandInHead.generate: prefix must be a PrefixCache made by this head's prefill_prefix")
+        if prefix.mode != self._mode():
+            raise F.LvqError(f"StandInHead.generate: the prefix was computed in precision mode {prefix.mode!r}, the head now runs {self._mode()!r}")
+        if prefix.version != self._weights_version():
+            raise F.LvqError("StandInHead.generate: the head's weights changed after prefill_prefix; compute the prefix again")
+        if prefix.plen.device != dev:
+            raise F.LvqError("StandInHead.generate: the prefix lives on another device")
+        if prefix_index is None:
+            if prefix.n_prefix != 1:
+                raise F.LvqError("StandInHead.generate: a PrefixCache of several prefixes needs prefix_index [B]")
+            prefix_index = torch.zeros(B, dtype=torch.int32, device=dev)
+        if not isinstance(prefix_index, torch.Tensor) or prefix_index.is_floating_point() or prefix_index.dtype == torch.bool \
+                or tuple(prefix_index.shape) != (B,):
+            raise F.LvqError(f"StandInHead.generate: prefix_index must be an integer tensor of shape [{B}]")
+        pidx = prefix_index.to(device=dev, dtype=torch.long)
+        if not bool(((pidx >= 0) & (pidx < prefix.n_prefix)).all()):
+            raise F.LvqError(f"StandInHead.generate: prefix_index must lie in 0 .. {prefix.n_prefix - 1}")
+        if prompt_lengths is None:
+            prompt_lengths = torch.full((B,), L, dtype=torch.int32, device=dev)
+        emb, qlen = self._ragged_prompts(inputs_embeds, attention_mask, prompt_lengths)
+        return emb, qlen, pidx.to(torch.int32).contiguous()
+
+    def _extend_shared(self, layers_arr, prefix_arr, prefix, pidx, rows, B, lq, own0, qn, t, lown, prec, ws):
+        """lvq_qwen2_extend_shared on rows [B * lq, d] fp32, in place: sequence b continues prefix pidx[b] behind own0[b] + t own rows."""
+        c = self.cfg
+        rc = F.lib().lvq_qwen2_extend_shared(layers_arr, prefix_arr, F.cint(len(self.model.layers)), F.ptr(rows), F.cint(B), F.cint(lq),
+                                             F.cint(c["d"]), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.ptr(pidx),
+                                             F.ptr(prefix.plen), F.cint(prefix.n_prefix), F.cint(prefix.pmax), F.ptr(own0), F.ptr(qn), F.cint(t),
+                                             F.cint(lown), F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec), F.ptr(ws),
+                                             F.csize(ws.numel()), F.stream_ptr(rows.device))
+        F.check(rc, "lvq_qwen2_extend_shared")
+
     @torch.no_grad()
     def generate(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None, max_new_tokens: int = 64,
                  do_sample: bool = False, num_beams: int = 1, pad_token_id: Optional[int] = None,
                  eos_token_id: Optional[int] = None, output_scores: bool = False, temperature: float = 1.0, top_k: Optional[int] = 50,
-                 top_p: float = 1.0, generator: Optional[torch.Generator] = None, prompt_lengths: Optional[torch.Tensor] = None, **unused):
+                 top_p: float = 1.0, generator: Optional[torch.Generator] = None, prompt_lengths: Optional[torch.Tensor] = None,
+                 prefix: Optional[PrefixCache] = None, prefix_index: Optional[torch.Tensor] = None, **unused):
         """`base_model.generate(inputs_embeds=, attention_mask=, max_new_tokens=, temperature=, top_p=, top_k=, do_sample=,
         num_beams=1, pad_token_id=, eos_token_id=)` as inference_engine.py:283-296 calls it, with a per-layer KV cache.
         do_sample=False: greedy (first maximum).  do_sample=True (the reference's default, temperature 0.7 / top_k 50 / top_p 0.9):
@@ -258,14 +339,24 @@ class StandInHead(_HipModule):
         are padding (zeroed here; attention_mask is None or the matching right-padded mask).  The prefill is the same causal call
         over L rows (padding lies behind the real rows, so causality keeps it out of them), the first logits come from row len_b-1,
         and every decode step is one lvq_qwen2_decode_step_ragged call with sequence b at position len_b + t, so each sequence sees
-        what it would see alone.  Ragged calls exist in the native step only: with LVQ_DECODE_PYTHON set they raise LvqError."""
+        what it would see alone.  Ragged calls exist in the native step only: with LVQ_DECODE_PYTHON set they raise LvqError.
+
+        prefix = a `PrefixCache` of this head's `prefill_prefix`, prefix_index = int tensor [B] (optional for a cache of one prefix):
+        sequence b CONTINUES prefix prefix_index[b].  inputs_embeds [B, Lq, d] then holds only the rows behind the prefix and
+        prompt_lengths (default: Lq for all) counts those rows.  The prefix rows are neither recomputed nor copied: the question prefill
+        is one lvq_qwen2_extend_shared call (csrc/decode_shared.hip) and every decode step is one more with one query row per sequence,
+        reading the prefix K / V in place; the sequence's own caches hold Lq + max_new_tokens rows.  A prefix from another head,
+        from other weights or from another precision mode raises LvqError, and so does LVQ_DECODE_PYTHON."""
         self._guard(inputs_embeds)
         if num_beams != 1:
             raise F.LvqError("StandInHead.generate: beam search is not implemented (num_beams must be 1)")
         if do_sample and not (temperature > 0.0 and 0.0 < top_p <= 1.0):
             raise ValueError("temperature must be > 0 and top_p in (0, 1]")
-        ragged = prompt_lengths is not None
-        if not ragged and attention_mask is not None and not bool((attention_mask == 1).all()):
+        shared = prefix is not None
+        if prefix_index is not None and not shared:
+            raise F.LvqError("StandInHead.generate: prefix_index without a prefix")
+        ragged = prompt_lengths is not None and not shared
+        if not ragged and not shared and attention_mask is not None and not bool((attention_mask == 1).all()):
             raise F.LvqError("StandInHead.generate expects an all-ones attention_mask (the reference builds exactly that)")
         c = self.cfg
         B, L, d = inputs_embeds.shape
@@ -273,23 +364,46 @@ class StandInHead(_HipModule):
         dev = inputs_embeds.device
         if ragged:
             inputs_embeds, pos0 = self._ragged_prompts(inputs_embeds, attention_mask, prompt_lengths)
-        lmax = L + max_new_tokens
+        elif shared:
+            inputs_embeds, qlen, pidx = self._shared_prompts(inputs_embeds, attention_mask, prompt_lengths, prefix, prefix_index)
+        lmax = L + max_new_tokens                              # with a prefix: rows of the sequences' OWN caches
         split = self._split()
         mk = lambda: (torch.empty((B, lmax, dkv), dtype=torch.bfloat16, device=dev),
                       torch.empty((B, lmax, dkv), dtype=torch.bfloat16, device=dev) if split else None)
         cache = [(mk(), mk()) for _ in self.model.layers]
-        x = self._layers(_f32(inputs_embeds).view(B * L, d), B, L, 0, cache)          # prefill
         native = not os.environ.get("LVQ_DECODE_PYTHON")       # decode steps: one native call per token (csrc/decoder.hip)
+        if shared and not native:
+            raise F.LvqError("StandInHead.generate: a call with a prefix has no Python-driven decode loop; unset LVQ_DECODE_PYTHON")
+        if not shared:
+            x = self._layers(_f32(inputs_embeds).view(B * L, d), B, L, 0, cache)      # prefill
         if ragged and not native:
             raise F.LvqError("StandInHead.generate: a ragged batch (prompt_lengths) has no Python-driven decode loop; unset LVQ_DECODE_PYTHON")
-        if native:
+        if shared:
+            lib = F.lib()
+            layers_arr, keep = self._native_layers(cache)
+            prec = 3 if split else 1
+            prefix_arr = (_Qwen2PrefixPtrs * len(self.model.layers))()
+            for i, ((kh, kl), (vh, vl)) in enumerate(prefix.layers):
+                prefix_arr[i] = _Qwen2PrefixPtrs(kh.data_ptr(), None if kl is None else kl.data_ptr(), vh.data_ptr(),
+                                                 None if vl is None else vl.data_ptr())
+            nbytes = max(int(lib.lvq_qwen2_extend_shared_workspace_bytes(F.cint(B), F.cint(lq), F.cint(d), F.cint(c["n_heads"]),
+                                                                         F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(prefix.pmax),
+                                                                         F.cint(lmax), F.cint(prec))) for lq in (L, 1))
+            step_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            zeros, ones = torch.zeros(B, dtype=torch.int32, device=dev), torch.ones(B, dtype=torch.int32, device=dev)
+            extend = lambda rows, lq, own0, qn, t: self._extend_shared(layers_arr, prefix_arr, prefix, pidx, rows, B, lq, own0, qn, t, lmax,
+                                                                       prec, step_ws)
+            x = _f32(inputs_embeds).view(B * L, d)             # _shared_prompts made this copy: the call works in place
+            extend(x, L, zeros, qlen, 0)                       # question prefill: own rows 0 .. qlen[b]-1
+            pos0 = qlen
+        elif native:
             lib = F.lib()
             layers_arr, keep = self._native_layers(cache)
             prec = 3 if split else 1
             ws_query = lib.lvq_qwen2_decode_ragged_workspace_bytes if ragged else lib.lvq_qwen2_decode_workspace_bytes
             nbytes = ws_query(F.cint(B), F.cint(d), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(lmax), F.cint(prec))
             step_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        if ragged:                                             # last real row of every sequence
+        if ragged or shared:                                   # last real row of every sequence
             last = x.view(B, L, d)[torch.arange(B, device=dev), pos0.long() - 1].contiguous()
         else:
             last = x.view(B, L, d)[:, -1].contiguous()
@@ -311,7 +425,9 @@ class StandInHead(_HipModule):
             if t + 1 == max_new_tokens:
                 break
             x = self.embed(nxt).float().contiguous()
-            if ragged:                                         # sequence b at position pos0[b] + t (csrc/decode_ragged.hip)
+            if shared:                                         # sequence b: own row qlen[b] + t, one query row (csrc/decode_shared.hip)
+                extend(x, 1, qlen, ones, t)
+            elif ragged:                                         # sequence b at position pos0[b] + t (csrc/decode_ragged.hip)
                 rc = lib.lvq_qwen2_decode_step_ragged(layers_arr, F.cint(len(self.model.layers)), F.ptr(x), F.cint(B), F.cint(d),
                                                       F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.ptr(pos0), F.cint(t),
                                                       F.cint(lmax), F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec),

@@ -204,6 +204,44 @@ def attention_decode_ragged(q: BF, k_cache: BF, v_cache: BF, kv_len: torch.Tenso
     return oh, ol
 
 
+def attention_extend_shared(q: BF, pk_cache: BF, pv_cache: BF, k_cache: BF, v_cache: BF, prefix_index: torch.Tensor, plen: torch.Tensor,
+                            own0: torch.Tensor, qn: torch.Tensor, *, n_heads: int, n_kv_heads: int, dh: int, scale: float) -> BF:
+    """Ragged chunks of query rows behind shared prefixes (include/lvq.h: lvq_attention_extend_shared).  q: BF [batch, lq, n_heads*dh];
+    prefix caches BF [n_prefix, pmax, n_kv_heads*dh]; own caches BF [batch, lown, n_kv_heads*dh] (they already hold the keys / values of
+    the query rows at own0[b] .. own0[b] + qn[b] - 1); prefix_index / own0 / qn: int32 [batch], plen: int32 [n_prefix], all on the device.
+    Every tensor contiguous.  Returns BF [batch, lq, n_heads*dh] (lo part when q is split)."""
+    qh, ql = q
+    dev = qh.device
+    batch, lq, d = qh.shape
+    n_prefix, pmax, dkv = pk_cache[0].shape
+    lown = k_cache[0].shape[1]
+    if d != n_heads * dh or dkv != n_kv_heads * dh or tuple(k_cache[0].shape) != (batch, lown, dkv):
+        raise F.LvqError("attention_extend_shared: q [batch, lq, H*dh], prefix caches [G, pmax, Hkv*dh], own caches [batch, lown, Hkv*dh]")
+    for name, t, n in (("prefix_index", prefix_index, batch), ("plen", plen, n_prefix), ("own0", own0, batch), ("qn", qn, batch)):
+        if t.dtype != torch.int32 or t.device != dev or t.numel() != n or not t.is_contiguous():
+            raise F.LvqError(f"attention_extend_shared: {name} must be a contiguous int32 tensor [{n}] on the operands' device")
+    split = ql is not None
+    F.require_cuda(qh, ql, *pk_cache, *pv_cache, *k_cache, *v_cache)
+    oh, ol = _bf_empty((batch, lq, d), dev, split)
+    L = F.lib()
+    nbytes = L.lvq_attention_extend_shared_workspace_bytes(F.cint(batch), F.cint(lq), F.cint(n_heads), F.cint(n_kv_heads), F.cint(pmax),
+                                                           F.cint(lown), F.cint(dh), F.cint(3 if split else 1))
+    key = (dev.index, "attn_shared")
+    ws = _ATT_WS.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+        _ATT_WS[key] = ws
+    rc = L.lvq_attention_extend_shared(
+        F.ptr(qh), F.ptr(ql), F.ptr(pk_cache[0]), F.ptr(pk_cache[1]), F.ptr(pv_cache[0]), F.ptr(pv_cache[1]), F.ptr(k_cache[0]),
+        F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(prefix_index), F.ptr(plen), F.ptr(own0), F.ptr(qn), F.cint(batch),
+        F.cint(lq), F.cint(n_heads), F.cint(n_kv_heads), F.cint(n_prefix), F.cint(pmax), F.cint(lown), F.cint(dh),
+        F.i64(lq * d), F.i64(d), F.i64(dh), F.i64(pmax * dkv), F.i64(lown * dkv), F.i64(dkv), F.i64(dh),
+        F.i64(pmax * dkv), F.i64(lown * dkv), F.i64(dkv), F.i64(dh), F.i64(lq * d), F.i64(d), F.i64(dh), F.cfloat(scale), F.ptr(oh), F.ptr(ol),
+        F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+    F.check(rc, f"lvq_attention_extend_shared (B={batch}, lq={lq}, H={n_heads}, Hkv={n_kv_heads}, G={n_prefix}, pmax={pmax}, lown={lown}, dh={dh})")
+    return oh, ol
+
+
 def ca_fused_ok(batch: int, nq: int, nkv: int, d: int, n_heads: int) -> bool:
     """Shapes of the fused short-K/V cross-attention kernel (include/lvq.h: lvq_ca_fused_ok)."""
     return bool(F.lib().lvq_ca_fused_ok(F.cint(batch), F.cint(nq), F.cint(nkv), F.cint(d), F.cint(n_heads)))
