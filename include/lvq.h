@@ -48,13 +48,14 @@ const char *lvq_strerror(int code);
 /* Kernel-family choices that are not implied by the shapes: every routing decision that used to hide behind a getenv inside the library
  * (VERDICT r2).  All zeros = the built-in choices (lvq_tuning_defaults).  Process-wide: set it before launching, not concurrently with
  * launches of other threads.  The Python mirror fills it from the LVQ_* environment variables of INTEGRATION.md (lidar-vision-vqa_amd/_ffi.py);
- * all variants of one entry point are held to the same oracle by the tests. */
+ * all variants of one entry point are held to the same oracle by the tests (for lvq_gemm_bf16 and lvq_attention_bf16:
+ * tests/test_gpu_kernel_routes.py, every field below that routes them against fp64). */
 typedef struct lvq_tuning {
     int32_t attn_no32;               /* 1: the 16x16x32 attention kernel for long K/V streams instead of k_attn32 */
     int32_t attn32_nw;               /* k_attn32 waves per workgroup: 0 auto, 4 or 6 */
     int32_t attn_pipe;               /* k_attn32 with 4 waves: 0 auto (pipelined for hi + lo / fp16 queries), 1 always pipelined, -1 never */
     int32_t attn_nsplit;             /* KV split count of the attention kernels: 0 auto, 1..64 (test hook: 1 = direct output path) */
-    int32_t attn_qt;                 /* k_attn query tiles per wave: 0 auto, 1, 2 or 4 */
+    int32_t attn_qt;                 /* k_attn query tiles per wave: 0 auto, 1 or 2 (other values are ignored) */
     int32_t attn_nw;                 /* k_attn waves per workgroup: 0 auto, 4, 8 or 12 */
     int32_t gemm_no_gemv;            /* 1: MFMA tile kernels also for M <= 8 (instead of the skinny-M GEMV) */
     int32_t gemm_stream_c_mb;        /* output size (MB) from which GEMM outputs use non-temporal stores: 0 = 32, -1 = never */
@@ -235,7 +236,8 @@ int lvq_bf16_to_f32(const lvq_bf16 *hi, const lvq_bf16 *lo, int64_t n, float alp
  *   element (b,i,h,e) of q lives at q[b*q_bstride + i*ldq + h*q_hstride + e] (same for k, v, o), so packed
  *   [B,N,3d] in_proj outputs and [B,H,S,D] tensors are both addressable without a copy.
  *   bias (optional, fp32 [B,H,Nq,Nkv]); causal != 0 adds the lower-triangular mask aligned to the END
- *   (query i sees keys j <= i + Nkv - Nq), used by the stand-in decoder head.
+ *   (query i sees keys j <= i + Nkv - Nq), used by the stand-in decoder head.  With Nq > Nkv the first Nq - Nkv queries see no
+ *   key at all: their output rows (o and o_lo) are ZERO on every path (fused kernels, KV-split combine, split path).
  *   n_kv_heads < n_heads => grouped-query attention (head h reads kv head h / (n_heads/n_kv_heads)).
  *   Online softmax, statistics and accumulation in fp32.  dh multiple of 16 and <= 128: fused flash
  *   kernel, no workspace.  Larger dh (448, 1024: the reference's 2-head defaults) or dh % 16 == 8: split
@@ -373,7 +375,7 @@ int lvq_attention_bf16(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *
  * and one kernel that takes the fp32 queries through LayerNorm, the Q projection, softmax(Q K^T / sqrt(dh)) V, the out projection,
  * bias and the fp32 residual without an activation round trip through HBM.  BASELINE.json's metric shape is
  * (batch, nq, nkv, d, n_heads) = (1, 32768, 196, 768, 12).
- *   lvq_ca_fused_ok       1 for the shapes the kernel family takes: d = 768, n_heads = 12 (head_dim 64), nq % 32 == 0, 1 <= nkv <= 224.
+ *   lvq_ca_fused_ok       1 for the shapes the kernel family takes: d = 768, n_heads = 12 (head_dim 64), nq % 32 == 0, 192 < nkv <= 224 (seven 32-key blocks: the only instantiation).
  *   lvq_ca_fused_pack     once per weights version: ln_gamma / ln_beta [d] (ca_ln), in_proj_w [3d, d], in_proj_b [3d], out_w [d, d],
  *                         out_b [d] (ca.in_proj_weight / in_proj_bias / out_proj.*) -> `packed` (lvq_ca_fused_packed_bytes): MFMA-fragment-
  *                         major 16-bit copies (gamma folded into W_q, beta and 1/sqrt(dh) into its bias).  f16 = 0: bf16 operands;

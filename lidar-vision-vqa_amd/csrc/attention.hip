@@ -1424,15 +1424,19 @@ AttnPlan plan_attn(int batch, int n_heads, int nq, int nkv, int dh, bool split, 
         return p;
     }
     const int dhp = (dh + 31) / 32 * 32;
-    int qmax = (dhp <= 64 && !split) ? 4 : 2;
+    // k_attn is instantiated for one and two query tiles per wave (launch_attn).  attn_qt = 4 used to be accepted here for
+    // dhp <= 64 plain: the plan then counted 64 queries per wave while the QT = 2 kernel covers 32, and every second block of
+    // 32 * nw queries was never written.  It is ignored now, like any other value without an instantiation.
+    int qmax = 2;
     if (dhp > 64 && split) qmax = 1;
     // Measured on MI355X (tools/bench_kernels.py attn, LVQ_ATTN_QT sweep): one 16-query tile per wave (4 waves/SIMD
-    // resident) beats 2 or 4 tiles per wave on every shape tried -- occupancy hides the softmax VALU and the
+    // resident) beats 2 tiles per wave on every shape tried (a setting of 4 never had a kernel of its own: it launched the
+    // two-tile kernel on half the workgroups, so it measured nothing) -- occupancy hides the softmax VALU and the
     // staging latency better than K/V fragment reuse saves LDS reads.
     p.qt = (dhp >= 96 && !split) ? 2 : 1;             // head_dim 96/128: two tiles per wave measured faster (377 vs 267 TFLOP/s)
     if (lvq_tune().attn_qt) {      // tuning knob (tools/bench_kernels.py); not used in production
         const int f = lvq_tune().attn_qt;
-        if ((f == 1 || f == 2 || f == 4) && f <= qmax) p.qt = f;
+        if ((f == 1 || f == 2) && f <= qmax) p.qt = f;
     }
     // waves per workgroup: long K/V streams are bandwidth-bound on re-reads -> as many queries per stream as fit
     p.nw = 4;
