@@ -96,11 +96,26 @@ def vat_lidar_tokens(bev: torch.Tensor, sd: SD) -> torch.Tensor:
     x = torch.einsum("bchw,dc->bhwd", x, sd["proj.weight"].view(d, C)) + sd["proj.bias"]
     x = x.reshape(B, H * W, d)
     x = layer_norm(x, sd["norm_tokens.weight"], sd["norm_tokens.bias"])
-    geom, sid = lidar_grid(H, W)
-    pe = gelu(geom @ sd["geo_mlp.0.weight"].t() + sd["geo_mlp.0.bias"]) @ sd["geo_mlp.2.weight"].t() + sd["geo_mlp.2.bias"]
+    pe, ve = lidar_pe(H, W, sd)
     x = x + pe.unsqueeze(0)
-    x = x + sd["view_embed"][sid].unsqueeze(0)
+    x = x + ve.unsqueeze(0)
     return x
+
+
+def lidar_pe(H: int, W: int, sd: SD) -> Tuple[torch.Tensor, torch.Tensor]:
+    """vat_lidar.py:236-248: (geo_mlp(geom) [HW, d], view_embed[sid] [HW, d]) in the dtype of the weights."""
+    geom, sid = lidar_grid(H, W)
+    geom = geom.to(sd["geo_mlp.0.weight"].dtype)
+    pe = gelu(geom @ sd["geo_mlp.0.weight"].t() + sd["geo_mlp.0.bias"]) @ sd["geo_mlp.2.weight"].t() + sd["geo_mlp.2.bias"]
+    return pe, sd["view_embed"][sid]
+
+
+def vat_lidar_kv(bev: torch.Tensor, sd: SD, layer: int = 0) -> torch.Tensor:
+    """The K|V input of block `layer`'s cross-attention, unfolded: vat_lidar_tokens -> in_proj rows d..3d (vat_blocks.py:42) -> [B,HW,2d]."""
+    x = vat_lidar_tokens(bev, sd)
+    d = x.shape[-1]
+    p = f"blocks.{layer}.ca."
+    return x @ sd[p + "in_proj_weight"][d:].t() + sd[p + "in_proj_bias"][d:]
 
 
 def vat_lidar(bev: torch.Tensor, sd: SD, n_heads: int) -> torch.Tensor:

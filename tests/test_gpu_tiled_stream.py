@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 from lidar_vision_vqa_amd import pipeline as P  # noqa: E402
 from lidar_vision_vqa_amd import synth  # noqa: E402
 from oracle import pipeline_oracle as PO  # noqa: E402
+from oracle.bev_tiles_oracle import bookkeeping as _np_bookkeeping  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -29,42 +30,6 @@ def random_pillars(B, H, W, M, seed, C=64):
     coords = torch.stack((cells // (H * W), torch.zeros_like(cells), (cells // W) % H, cells % W), 1).to(torch.int32)
     feat = torch.from_numpy(synth.randn((M, C), seed + 1))
     return coords.to(DEV).contiguous(), feat.to(DEV)
-
-
-def _np_bookkeeping(occ, row_base):
-    """numpy restatement of lvq_bev_tiles: occ [B, H, W] bool -> (live codes, piece_dirty, row_src [B, HW], counts)."""
-    B, H, W = occ.shape
-    tw = W // 8
-    nt = (H // 8) * tw
-    pad = np.pad(occ, ((0, 0), (1, 1), (1, 1)))
-    dirty = np.zeros((B, H, W), bool)                                             # a pillar in the 3 x 3 neighbourhood
-    for dy in range(3):
-        for dx in range(3):
-            dirty |= pad[:, dy:dy + H, dx:dx + W]
-    mask = np.zeros((B, nt, 8), np.int64)                                         # bit j = 4 cy + cx of piece p (rows 2 (p >> 1) .., columns 4 (p & 1) ..)
-    for t in range(nt):
-        for p in range(8):
-            y0, x0 = (t // tw) * 8 + (p >> 1) * 2, (t % tw) * 8 + (p & 1) * 4
-            for j in range(8):
-                mask[:, t, p] |= dirty[:, y0 + (j >> 2), x0 + (j & 3)].astype(np.int64) << j
-    codes, pdirty = [], []
-    row_src = np.empty((B, nt * 64), np.int64)
-    nd = 0
-    for t in range(nt):
-        for s in range(B):
-            for p in range(8):
-                m = int(mask[s, t, p])
-                if m:
-                    codes.append((t * B + s) * 8 + p)
-                    pdirty.append((nd, m))
-                for j in range(8):
-                    e = 64 * t + 8 * p + j
-                    if (m >> j) & 1:
-                        row_src[s, e] = row_base + nd
-                        nd += 1
-                    else:
-                        row_src[s, e] = e
-    return codes, pdirty, row_src, (len(codes), 8 * len(codes), nd)
 
 
 @pytest.mark.parametrize("B,H,W,M", [(3, 64, 64, 40), (1, 128, 96, 900), (2, 32, 32, 0), (2, 16, 24, 5000)])
