@@ -487,6 +487,64 @@ int lvq_sparse_to_dense(const float *feats, const int32_t *indices, int index_co
                         int c, int batch, int d, int h, int w, float *out, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
 /* =====================================================================================
+ * Sparse convolution backbone (csrc/sparse_conv.hip): the layers of VoxelResBackBone8xVoxelNeXt
+ * ===================================================================================== */
+
+/* Semantics (spconv 2.x, as pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225 uses it through pcdet/utils/spconv_utils.py:1-30).
+ *   tensor    features [N, C] fp32, indices [N, 1 + nd] int32 = (b, z, y, x) or (b, y, x), spatial_shape (D, H, W) or (H, W), batch.
+ *             The index rows of one tensor are distinct (as spconv requires); a row outside the grid or the batch takes no part.
+ *   weight    [C_out, kz, ky, kx, C_in] (2-D: [C_out, ky, kx, C_in]), spconv 2.x's layout.  The convolution is a CROSS-CORRELATION: it
+ *             equals torch.nn.functional.conv3d(dense input, weight.permute(0, 4, 1, 2, 3)).  Kernel offset o = (oz * ky + oy) * kx + ox.
+ *   submanifold conv (SubMConv3d / SubMConv2d; odd kernel <= 3, stride 1): the output rows are the input rows, in the same order;
+ *             out[i] = bias + sum_o W[:, o, :] . in[row(c_i + o - k/2)] over the offsets whose neighbour is an active row of the same
+ *             scene inside the grid.  An absent neighbour contributes nothing.
+ *   regular conv (SparseConv3d / SparseConv2d; kernel <= 3, stride s, padding p < k): output shape floor((D + 2p - k) / s) + 1 per
+ *             axis; site q is active iff some input q * s - p + o is active and inside the grid; out[q] = sum_o W[:, o, :] . in[row(q * s - p + o)].
+ *             spconv leaves the order of the output rows unspecified; here they ascend in (b, z, y, x).  Everything downstream
+ *             (lvq_sparse_bev_merge, lvq_sparse_to_dense, further rules) addresses rows through their coordinates.
+ *   epilogue  y = [relu]((acc + bias) * scale + shift [+ residual[i]]),  scale = gamma / sqrt(var + eps), shift = beta - mean * scale of
+ *             an eval-mode BatchNorm1d (eps 1e-3 in the backbone, 1e-5 in shared_conv's default nn.BatchNorm1d).
+ *   order     offsets are summed in ascending o for every row, channels in ascending order inside an offset, fp32 accumulation; a
+ *             row's bits depend on its own neighbours only -- not on its tile or its position: permuting the input rows of a
+ *             submanifold conv permutes the output rows bit for bit, and two runs give the same bits (no atomics on outputs).
+ *
+ * lvq_sparse_conv_rules: the active output set and the neighbour table of one layer geometry (spconv's "indice pairs"; layers that share
+ * an indice_key share one table).
+ *   indices        [n_in, 1 + ndim] int32;  spatial_shape / kernel / stride / padding: HOST int32[ndim] in (z, y, x) or (y, x) order
+ *                  (stride / padding are ignored, and may be NULL, for subm != 0)
+ *   out_indices    [out_cap, 1 + ndim] int32, ascending (b, z, y, x); not touched for subm (the output indices are the input's)
+ *   nbr            [out_cap, K] int32, K = prod(kernel) <= 27: input row of offset o, -1 = absent
+ *   n_out_dev      device int32: the number of output rows (n_in for subm).  It may exceed out_cap: rows past out_cap are not
+ *                  written, and the caller repeats the call with more room; out_cap >= min(n_in * prod(ceil(k / s)), output cells)
+ *                  always suffices.  subm needs out_cap >= n_in.  Rows at and behind the count are never written.
+ * Keys are ((b D + z) H + y) W + x in int32: a key space (input or output grid, times batch) of 2^31 or more returns LVQ_EOVERFLOW
+ * before anything is launched (one scene of 41 x 1440 x 1440 fits; 26 do not).  Every axis is range-checked before a key is formed, so
+ * a neighbour across an x, y, z or scene edge reads as absent.  No hash table: the ascending-unique kernels of lvq_voxelize_dynamic rank
+ * the cells, neighbours are found by a binary search of at most 32 steps -- every loop has a bound known at launch. */
+size_t lvq_sparse_conv_rules_workspace_bytes(int64_t n_in, int ndim, const int32_t *spatial_shape_host, int batch, const int32_t *kernel_host,
+                                             const int32_t *stride_host, const int32_t *padding_host, int subm);
+int lvq_sparse_conv_rules(const int32_t *indices, int64_t n_in, int ndim, const int32_t *spatial_shape_host, int batch,
+                          const int32_t *kernel_host, const int32_t *stride_host, const int32_t *padding_host, int subm, int64_t out_cap,
+                          int32_t *out_indices, int32_t *nbr, int32_t *n_out_dev, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* The convolution itself (spconv_backbone_voxelnext.py:8-66: conv + BatchNorm1d + ReLU of post_act_block, conv + bn + residual + relu
+ * of SparseBasicBlock) as a gather-form implicit GEMM on bf16 MFMA tiles with fp32 accumulation; semantics above.
+ *   lvq_sparse_conv_pack_weights   once per weights version: weight [C_out, K, C_in] fp32 -> w_hi (+ w_lo, or NULL) of
+ *                                  lvq_sparse_conv_packed_elems(c_out, k_vol, c_in) bf16 elements each ([K][C_out][C_in padded to 32]).
+ *   lvq_sparse_conv                feat [n_in, c_in] fp32, nbr [n_out_cap, k_vol] from lvq_sparse_conv_rules, out [n_out_cap, c_out] fp32.
+ *                                  w_lo != NULL: features and weights as hi + lo, three products (bf16x3); NULL: plain bf16 operands.
+ *                                  bias / scale + shift (both or neither) / residual [n_out_cap, c_out] may be NULL.  n_out_dev (device
+ *                                  int32, may be NULL = all n_out_cap rows; clamped to n_out_cap): rows at and behind it are not written.
+ *                                  A table entry outside [0, n_in) reads as absent.  No workspace.
+ * c_in in {4, 5, 16, 32, 64, 128}, c_out in {16, 32, 64, 128}, k_vol <= 27; anything else returns LVQ_EUNSUPPORTED.  w_hi / w_lo 16-byte
+ * aligned, feat 16-byte aligned when c_in % 4 == 0. */
+size_t lvq_sparse_conv_packed_elems(int c_out, int k_vol, int c_in);
+int lvq_sparse_conv_pack_weights(const float *weight, int c_out, int k_vol, int c_in, lvq_bf16 *w_hi, lvq_bf16 *w_lo, lvq_stream_t stream);
+int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nbr, int k_vol, int64_t n_out_cap, const int32_t *n_out_dev,
+                    const lvq_bf16 *w_hi, const lvq_bf16 *w_lo, int c_out, const float *bias, const float *scale, const float *shift,
+                    const float *residual, int relu, float *out, lvq_stream_t stream);
+
+/* =====================================================================================
  * Decode-step runtime
  * ===================================================================================== */
 
