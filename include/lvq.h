@@ -131,7 +131,13 @@ int lvq_mean_vfe(const float *voxels, const int32_t *num_pts, int64_t m_cap, con
  *   w/scale/shift: HOST arrays of n_layers DEVICE pointers; cin/cout: host int arrays.
  *   flags bit0 = USE_ABSLOTE_XYZ, bit1 = WITH_DISTANCE
  *   voxel geometry: vsize[3], offset[3] = vsize/2 + range_lo  (host)
- *   out [m, cout_last] fp32.   Limits: T <= 64, every cin/cout <= 256 (else LVQ_EUNSUPPORTED). */
+ *   out [m, cout_last] fp32; rows >= *n_voxels_dev (if given) are not written.
+ *   Shape rule.  LVQ_EINVAL: t <= 0, c < 3, n_layers < 1, cin_0 != (bit0 ? c : c - 3) + 6 + (bit1 ? 1 : 0), or
+ *   cin_l != 2 cout_{l-1} for l >= 1 (a non-final layer hands [x, x_max] on).  LVQ_EUNSUPPORTED: n_layers > 4, T > 64, a
+ *   cout_l > 256 or cin_l > 512, or T * cmax > 20480 with cmax = max(c, every cin_l, 2 cout_l of the non-final layers,
+ *   cout of the last): one wave keeps two [T][cmax] fp32 planes in LDS, and the workgroup shrinks from 4 waves to 2 to 1
+ *   until they fit in 160 KB.  So every T <= 40 runs at any width the other limits allow, T = 64 up to cmax = 320
+ *   (e.g. [64, 64] and [160, 256]), and T = 32 with cout = 256.  Nothing is written when a call is refused. */
 int lvq_pillar_vfe(const float *voxels, const int32_t *num_pts, const int32_t *coords_bzyx, int64_t m_cap,
                    const int32_t *n_voxels_dev, int t, int c, int n_layers, const float *const *w_host,
                    const float *const *scale_host, const float *const *shift_host, const int32_t *cin_host,
@@ -167,8 +173,10 @@ int lvq_scatter_mean(const float *pts, int64_t n, int c, int col0, int nc, const
  * (dynamic_pillar_vfe.py:35-46), BatchNorm folded as in lvq_pillar_vfe.
  *   kind 0 = pillar (f_center z = z - z_offset), 1 = voxel (per-cell z centre), 2 = simple2d (no f_cluster)
  *   points_mean [m,3] from lvq_scatter_mean (ignored for kind 2)
- *   n_layers <= 2; layer outputs cout_l <= 256.  xmax_tmp [m_cap, cout_0/1] scratch for 2-layer nets
- *   (zero on entry), out [m_cap, cout_last] zero on entry (post-ReLU maxima are >= 0). */
+ *   n_layers <= 2, cout_l <= 256, at most 16 augmented features (cin_0 = (bit0 ? c - 1 : c - 4) + (kind 2 ? 3 : 6) +
+ *   (bit1 ? 1 : 0)): otherwise LVQ_EUNSUPPORTED; a cin_0 other than that count or cin_1 != 2 cout_0: LVQ_EINVAL.
+ *   xmax_tmp [m_cap, cout_0] scratch for 2-layer nets (zero on entry), out [m_cap, cout_last] zero on entry (post-ReLU
+ *   maxima are >= 0; a voxel that receives no point keeps its zero). */
 int lvq_dynamic_pfn(const float *pts, int64_t n, int c, const int32_t *unq_inv, const int32_t *pt_coords,
                     const float *points_mean, int kind, int n_layers, const float *const *w_host,
                     const float *const *scale_host, const float *const *shift_host, const int32_t *cin_host,

@@ -66,7 +66,7 @@ __global__ void __launch_bounds__(256) k_pillar_vfe(const float *__restrict__ vo
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     int64_t m = n_live ? (int64_t)*n_live : m_cap;
     if (m > m_cap) m = m_cap;
-    const int64_t v = (int64_t)blockIdx.x * 4 + wid;
+    const int64_t v = (int64_t)blockIdx.x * (blockDim.x >> 6) + wid;  // 4, 2 or 1 waves per workgroup (lvq_pillar_vfe)
     if (v >= m) return;  // whole wave exits together; no block barrier is used below
     float *bufA = smem + (size_t)wid * 2 * T * cmax;
     float *bufB = bufA + (size_t)T * cmax;
@@ -409,7 +409,8 @@ __global__ void __launch_bounds__(256) k_pillar_scatter(const float *__restrict_
 
 int fill_params(PfnParams &P, int n_layers, const float *const *w, const float *const *scale, const float *const *shift,
                 const int32_t *cin, const int32_t *cout, int flags, const float *vs, const float *off) {
-    if (n_layers < 1 || n_layers > MAX_LAYERS || !w || !scale || !shift || !cin || !cout || !vs || !off) return LVQ_EINVAL;
+    if (n_layers < 1 || !w || !scale || !shift || !cin || !cout || !vs || !off) return LVQ_EINVAL;
+    if (n_layers > MAX_LAYERS) return LVQ_EUNSUPPORTED;
     P.n_layers = n_layers;
     P.flags = flags;
     for (int l = 0; l < n_layers; ++l) {
@@ -454,9 +455,13 @@ extern "C" int lvq_pillar_vfe(const float *voxels, const int32_t *num_pts, const
     }
     if (m_cap == 0) return LVQ_OK;
     if (!voxels || !num_pts || !coords_bzyx || !out) return LVQ_EINVAL;
-    size_t lds = (size_t)4 * 2 * t * cmax * sizeof(float);
+    // two [T][cmax] planes per wave: as many waves per workgroup (4, 2, 1) as fit the CU's 160 KB of LDS
+    const size_t per_wave = (size_t)2 * t * cmax * sizeof(float);
+    int wpb = 4;
+    while (wpb > 1 && per_wave * wpb > 160 * 1024) wpb >>= 1;
+    const size_t lds = per_wave * wpb;
     if (lds > 160 * 1024) return LVQ_EUNSUPPORTED;
-    dim3 grid((unsigned)lvq_cdiv(m_cap, 4)), block(256);
+    dim3 grid((unsigned)lvq_cdiv(m_cap, wpb)), block(64 * wpb);
     if (n_layers == 1 && c == 4 && t <= 32 && P.cin[0] <= 12 && P.cout[0] <= 64 && !(((uintptr_t)voxels) & 15) &&
         !lvq_tune().pillar_vfe_generic) {
         // 4 waves x 8 pillars per workgroup
