@@ -553,6 +553,47 @@ int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nb
                     const float *residual, int relu, float *out, lvq_stream_t stream);
 
 /* =====================================================================================
+ * Dense 2-D BEV backbone (csrc/conv2d.hip): the layers of BaseBEVBackbone / BaseBEVBackboneV1
+ * ===================================================================================== */
+
+/* Semantics (torch.nn.Conv2d / ConvTranspose2d / eval BatchNorm2d / ReLU as pcdet/models/backbones_2d/base_bev_backbone.py:6-204 stacks them).
+ *   planes    an activation is channels-last 16-bit operand planes [B, H, W, Cp] bf16, Cp = C rounded up to a multiple of 32 (zeros beyond
+ *             C): a hi plane and, for the bf16x3 form, a lo plane with hi + lo ~ the fp32 value.  lvq_conv2d_to_planes makes them from the
+ *             reference's [B, C, H, W] fp32 `spatial_features`; every conv writes the next conv's planes from its epilogue.
+ *   conv      cross-correlation, weight torch's [C_out, C_in, k, k]:  kernel 3, padding 1, stride 1 or 2 (output floor((H - 1) / s) + 1
+ *             per axis), or kernel = stride = s in {1, 2, 4}, padding 0 (output floor(H / s)).  lvq_conv2d_out_size is that rule.
+ *   deconv    ConvTranspose2d(kernel = stride = s), s in {1, 2, 4}, weight torch's [C_in, C_out, s, s]:
+ *             out[b, co, s y + i, s x + j] = sum_ci in[b, ci, y, x] W[ci, co, i, j]  (a GEMM with s^2 C_out columns + a pixel shuffle).
+ *   epilogue  y = [relu](acc * scale[co] + shift[co]); scale / shift both or neither (NULL = identity).
+ *   outputs   out_hi (+ out_lo) planes [B, OH, OW, out_c_total] and / or out_f32 [B, out_c_total, OH, OW] fp32 (the reference's
+ *             `spatial_features_2d` layout); at least one.  The layer writes channels out_c_off .. out_c_off + c_out - 1 of either and
+ *             nothing else: deblocks write straight into their range of the concatenated result.
+ *   forms     w_lo != NULL: hi + lo operands, three products (bf16x3), in_lo required; w_lo == NULL: plain bf16, in_lo must be NULL.
+ *   order     32-channel chunks ascending, taps (ky * k + kx) ascending inside a chunk of the staged tile, fp32 accumulation, no atomics:
+ *             a pixel's bits depend on its own receptive field only, not on its position, tile, scene or the canvas size.
+ * Family: c_in 1 .. 512 (the input planes hold c_in rounded up to 32 channels), c_out a multiple of 64 in 64 .. 512, batch <= 65535;
+ * a (kernel, stride) or channel count outside it returns LVQ_EUNSUPPORTED, an inconsistent call (non-positive size, NULL operand, one of
+ * scale / shift, in_lo without w_lo, out_c_off + c_out > out_c_total, a kernel = stride larger than the canvas) LVQ_EINVAL; both before
+ * any launch.  Plane and packed-weight pointers are 16-byte aligned.  No workspace, no allocation, stream-ordered.
+ *   lvq_conv2d_plane_elems     batch * h * w * (c rounded up to 32), 0 outside the family                              (host only)
+ *   lvq_conv2d_out_size        output size of one axis, or the negative error code                                     (host only)
+ *   lvq_conv2d_packed_elems    (c_in rounded up to 32) * kernel^2 * c_out bf16 elements per part, 0 outside the family (host only;
+ *                              transposed != 0: kernel is the stride s of the transposed conv)
+ *   lvq_conv2d_pack_weights    once per weights version: fp32 weight -> w_hi (+ w_lo, or NULL) in MFMA-fragment order */
+size_t lvq_conv2d_plane_elems(int batch, int c, int h, int w);
+int lvq_conv2d_out_size(int in, int kernel, int stride);
+int lvq_conv2d_to_planes(const float *x, int batch, int c, int h, int w, lvq_bf16 *hi, lvq_bf16 *lo, lvq_stream_t stream);
+size_t lvq_conv2d_packed_elems(int c_out, int c_in, int kernel, int transposed);
+int lvq_conv2d_pack_weights(const float *weight, int c_out, int c_in, int kernel, int transposed, lvq_bf16 *w_hi, lvq_bf16 *w_lo,
+                            lvq_stream_t stream);
+int lvq_conv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
+               int c_out, int kernel, int stride, const float *scale, const float *shift, int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo,
+               float *out_f32, int out_c_total, int out_c_off, lvq_stream_t stream);
+int lvq_deconv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
+                 int c_out, int stride, const float *scale, const float *shift, int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo, float *out_f32,
+                 int out_c_total, int out_c_off, lvq_stream_t stream);
+
+/* =====================================================================================
  * Decode-step runtime
  * ===================================================================================== */
 

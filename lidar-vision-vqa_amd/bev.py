@@ -186,3 +186,8 @@ class HeightCompression(nn.Module):
         batch_dict["spatial_features"] = spatial_features
         batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
         return batch_dict
+
+
+# map_to_bev/__init__.py's registry lives in lidar.py, which this module imports from: the entry is added from this side
+from . import lidar as _lidar  # noqa: E402
+_lidar.map_to_bev_all["HeightCompression"] = HeightCompression

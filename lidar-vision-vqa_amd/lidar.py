@@ -496,3 +496,4 @@ __all__ = {
     "DynamicVoxelVFE": DynamicVoxelVFE,
 }
 map_to_bev_all = {"PointPillarScatter": PointPillarScatter}
+from . import bev as _bev  # noqa: E402,F401  (bev.py ends by adding "HeightCompression" here: it imports `workspace` from this module, so it cannot be named above)
