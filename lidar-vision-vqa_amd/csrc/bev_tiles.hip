@@ -17,6 +17,7 @@
 // partials merged with Chan's formula) -> + positional table -> bf16 rows, without any intermediate in HBM.
 #include "common.h"
 #include <type_traits>
+#include <utility>
 
 namespace bt {
 
@@ -1132,6 +1133,30 @@ struct KvRowArgs {
     int k_fp16;
 };
 
+// The loads of k_kv_rows' tile loop as inline asm.  The compiler's wait pass does not count them, and that is the point: with an LDS-DMA
+// outstanding it waits vmcnt(0) at the first use of any load it does count and at every __syncthreads(), which put eight full drains
+// into a tile and made the "one group ahead" T request wait for itself.  Every load of the loop is therefore issued here, every wait is
+// a vm_wait<N>() counted by hand in the kernel, and a destination register is handed to the compiler (landed()) only behind the wait
+// that retires it.  Vector-memory operations complete in issue order, so vmcnt(N) retires everything but the newest N.
+template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+template <int OFF> __device__ __forceinline__ void vm_load16(f32x4 &d, const void *p) {       // early clobber: d never overlaps the address pair
+    asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=&v"(d) : "v"(p), "n"(OFF) : "memory");
+}
+template <class T> __device__ __forceinline__ void vm_load4(T &d, const void *p) {
+    static_assert(sizeof(T) == 4, "one dword");
+    asm volatile("global_load_dword %0, %1, off" : "=&v"(d) : "v"(p) : "memory");
+}
+// 16 B per lane global -> LDS at the wave-uniform LDS byte address `dst` + 16 lane (M0 is the compiler's: saved and restored)
+__device__ __forceinline__ void vm_dma16(const void *src, uint32_t dst) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+}
+// volatile asm statements keep their order: behind a vm_wait this makes every later use of x a use of the landed value
+template <class T> __device__ __forceinline__ void landed(T &x) { asm volatile("" : "+v"(x)); }
+template <int... I, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F &&f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for(std::make_integer_sequence<int, N>{}, f); }
+
 // TH: the table T is IEEE fp16 (its values are bounded by the fold; the rounding, 2^-12, disappears under the bf16 rounding of the result):
 // half the L2 traffic of the kernel's largest stream.  A lane then owns 8 consecutive columns per PAIR of column tiles, so one 16-byte
 // request still covers a full 64-byte line per cell.
@@ -1185,16 +1210,15 @@ __global__ void __launch_bounds__(512) k_kv_rows(KvRowArgs a) {
     auto colj = [&](int j) { return TH ? 32 * (j >> 1) + 4 * (j & 1) : 16 * j; };      // lane's column of tile j, relative to col0
     // stage the 64 contiguous t rows of tile g: wave w moves rows 8 w .. 8 w + 7 (one 1-KiB LDS-DMA for hi, one for lo); LDS position
     // (row, chunk c) receives SOURCE chunk c ^ ((row >> 1) & 7), the swizzle the fragment reads expect.  Rows past the end are clamped.
+    const uint32_t lds_t = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint16_t *)t_hi);
     auto stage = [&](int64_t g, int buf) {
         const int row = 8 * wid + (lane >> 3), c = lane & 7;
         int64_t r = g * TCELLS + row;
         r = r < n_rows ? r : n_rows - 1;
         const int64_t so = r * C + ((c ^ ((row >> 1) & 7)) << 3);
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.th + so),
-                                         (__attribute__((address_space(3))) void *)(t_hi + (buf * TCELLS + 8 * wid) * C), 16, 0, 0);
-        if (X3)
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.tl + so),
-                                             (__attribute__((address_space(3))) void *)(t_lo + (buf * TCELLS + 8 * wid) * C), 16, 0, 0);
+        const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_t + (uint32_t)((buf * TCELLS + 8 * wid) * C * 2));
+        vm_dma16(a.th + so, dst);
+        if (X3) vm_dma16(a.tl + so, dst + 2 * TCELLS * C * 2);        // t_lo
     };
     auto load_t = [&](int buf, int gq, bf16x8 &th0, bf16x8 &th1, bf16x8 &tl0, bf16x8 &tl1) {
         const int row = gq * 16 + l15;
@@ -1206,14 +1230,18 @@ __global__ void __launch_bounds__(512) k_kv_rows(KvRowArgs a) {
             tl1 = *reinterpret_cast<const bf16x8 *>(t_lo + (buf * TCELLS + row) * C + c1);
         }
     };
-    auto opaque = [](const float *p) { asm volatile("" : "+v"(p)); return p; };
+    // the bias is re-read from LDS at every use (24 more live registers would not fit).  What is laundered per use is its 32-bit LDS
+    // address: behind a laundered generic pointer the reads were FLAT loads, which count on vmcnt and lgkmcnt and can only be waited
+    // for with zero; these are ds_read_b128 on lgkmcnt alone.
+    const uint32_t lds_bias = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) float *)pbias) + 4 * col0;
     auto product = [&](auto hf_tag, const bf16x8 &th0, const bf16x8 &th1, const bf16x8 &tl0, const bf16x8 &tl1, f32x4 (&acc)[JH]) {
         constexpr int HF = decltype(hf_tag)::value;
-        const float *pb = opaque(pbias + col0);
+        uint32_t pb = lds_bias;
+        asm volatile("" : "+v"(pb));
 #pragma unroll
         for (int jj = 0; jj < JH; ++jj) {
             const int j = HF * JH + jj;
-            acc[jj] = *reinterpret_cast<const f32x4 *>(pb + colj(j));
+            acc[jj] = *(const __attribute__((address_space(3))) f32x4 *)(pb + 4 * colj(j));
             acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][0], th0, acc[jj], 0, 0, 0);
             acc[jj] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[j][1], th1, acc[jj], 0, 0, 0);
             if (X3) {
@@ -1225,64 +1253,95 @@ __global__ void __launch_bounds__(512) k_kv_rows(KvRowArgs a) {
         }
     };
     if (g_begin >= g_end) return;
+    // ---- vector-memory accounting of the tile loop.  Per wave and tile, in issue order (every tile issues all of it, so the counts
+    // hold on every path; the stores are the one exception, see `full`):
+    //     stage(next tile)  D LDS-DMA pieces        meta(next tile)  M key / rstd dwords
+    //     T1  R requests    [group 0: its wait W0]  E0  S output stores
+    //     T2  R             [group 1: W1]           E1  S
+    //     T3  R             [group 2: W2]           E2  S
+    //     T0' R (group 0 of the NEXT tile)  [group 3: W3]  E3  S
+    // Wq sits behind the MFMAs of group q and retires Tq; it is the only kind of wait in the loop, and what it leaves in flight is
+    // listed where it is written.  The stage DMA and the meta loads need no wait of their own: they are older than T1, so W1 retires
+    // them, three barriers before the staged rows are read (behind the next tile's first barrier) and before the keys are used (T0').
+    constexpr int R = TH ? JH : J;                                // 16-byte T requests per lane and 16-row group (64 B apart)
+    constexpr int S = N / 256;                                    // 16-byte output stores per lane and 16-row group
+    constexpr int D = X3 ? 2 : 1;                                 // LDS-DMA pieces per wave and tile
+    constexpr int M = 8;                                          // key + rstd dwords per lane and tile
+    // the compiler's own loads (M, m0) are used, hence complete, before the first hand-counted one: from here on the only
+    // vector-memory operations it counts are the output stores, which it never waits for
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        landed(wf[j][0]);
+        landed(wf[j][1]);
+        if (X3) { landed(wfl[j][0]); landed(wfl[j][1]); }
+    }
     // the lane's four rows of a tile (row 16 q + l15): key and rstd, fetched a whole tile ahead so that the T requests never wait on them
     auto load_meta = [&](int64_t g, int (&kq)[4], float (&rq)[4]) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             int64_t r = g * TCELLS + q * 16 + l15;
             r = r < n_rows ? r : n_rows - 1;
-            kq[q] = a.key[r];
-            rq[q] = a.rstd[r];
+            vm_load4(kq[q], a.key + r);
+            vm_load4(rq[q], a.rstd + r);
         }
     };
-    int kq[4];
-    float rq[4];
-    load_meta(g_begin, kq, rq);
-    stage(g_begin, 0);
+    auto meta_landed = [&](int (&kq)[4], float (&rq)[4]) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { landed(kq[q]); landed(rq[q]); }
+    };
+    // the lane's part of row `key` of T: R requests, raw (the fp16 form stays packed until its use)
+    auto request = [&](int key, f32x4 (&te)[R]) {
+        const char *tep = TH ? reinterpret_cast<const char *>(reinterpret_cast<const uint16_t *>(a.te) + (int64_t)key * (2 * N) + ncol0 + col0)
+                             : reinterpret_cast<const char *>(a.te + (int64_t)key * (2 * N) + ncol0 + col0);
+        static_for<R>([&](auto i) { vm_load16<64 * decltype(i)::value>(te[decltype(i)::value], tep); });
+    };
+    int kq[4], kn[4];
+    float rq[4], rn[4];
+    f32x4 te_a[R], te_b[R];
+    load_meta(g_begin, kq, rq);                                   // M
+    stage(g_begin, 0);                                            // D
+    vm_wait<D>();                                                 // in flight: meta M, stage D.  Retires the meta loads.
+    meta_landed(kq, rq);
+    request(kq[0], te_a);                                         // R (T0 of the first tile)
+    vm_wait<R>();                                                 // in flight: stage D, T0 R.  Retires the stage: read behind the loop's first barrier.
     int buf = 0;
     for (int64_t g = g_begin; g < g_end; g += g_step) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's rows of tile g have landed (requested a whole tile ago)
-        __syncthreads();                                          // tile g complete for everyone; everyone is done reading the other buffer
-        const bool has_nx = g + g_step < g_end;
-        if (has_nx) stage(g + g_step, buf ^ 1);
-        int kn[4] = {0, 0, 0, 0};
-        float rn[4] = {0.f, 0.f, 0.f, 0.f};
-        if (has_nx) load_meta(g + g_step, kn, rn);
-        // the rows of T are requested one 16-row group ahead of their use
-        auto request = [&](int gq, f32x4 (&te)[2 * JH], float &rs, bool &valid) {
-            valid = g * TCELLS + gq * 16 + l15 < n_rows;
-            rs = gq == 0 ? rq[0] : gq == 1 ? rq[1] : gq == 2 ? rq[2] : rq[3];
-            const int key = gq == 0 ? kq[0] : gq == 1 ? kq[1] : gq == 2 ? kq[2] : kq[3];
-            if (TH) {                                               // 8 halfs (tiles 2 p, 2 p + 1) per request, kept packed until their use
-                const uint16_t *tep = reinterpret_cast<const uint16_t *>(a.te) + (int64_t)key * (2 * N) + ncol0 + col0;
-#pragma unroll
-                for (int p2 = 0; p2 < JH; ++p2) {
-                    const u32x4 v = *reinterpret_cast<const u32x4 *>(tep + 32 * p2);
-                    te[2 * p2] = f32x4{__uint_as_float(v[0]), __uint_as_float(v[1]), 0.f, 0.f};
-                    te[2 * p2 + 1] = f32x4{__uint_as_float(v[2]), __uint_as_float(v[3]), 0.f, 0.f};
-                }
-            } else {
-                const float *tep = a.te + (int64_t)key * (2 * N) + ncol0 + col0;
-#pragma unroll
-                for (int jj = 0; jj < 2 * JH; ++jj) te[jj] = *reinterpret_cast<const f32x4 *>(tep + 16 * jj);
-            }
-        };
-        auto emit = [&](int gq, const f32x4 (&te)[2 * JH], const float rs, const bool valid) {
+        // first: no E3 of a previous tile lies between T0 and this tile's stage.  full: all 64 rows exist, so every wave issues every
+        // one of its output stores; in the one partial tile a wave whose rows are all past the end branches around a store, so
+        // there the waits do not count the stores (with the stores issued after all, that waits for them too: safe)
+        const bool first = g == g_begin, full = (g + 1) * TCELLS <= n_rows;
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();                             // tile g complete for everyone (its DMA retired by W1..W3 of the previous tile, or above); everyone is done reading the other buffer
+        asm volatile("" ::: "memory");
+        const int64_t gn = g + g_step < g_end ? g + g_step : g;   // a workgroup's last tile stages and requests itself again: same counts, in-bounds, unused
+        stage(gn, buf ^ 1);                                       // D
+        load_meta(gn, kn, rn);                                    // M
+        auto emit = [&](int gq, f32x4 (&te)[R], auto &&wait) {
             bf16x8 th0, th1, tl0, tl1;
             load_t(buf, gq, th0, th1, tl0, tl1);
+            const float rs = gq == 0 ? rq[0] : gq == 1 ? rq[1] : gq == 2 ? rq[2] : rq[3];
             uint16_t *sb = sbuf + (gq & 1) * 16 * SROW;
             uint16_t *dst = sb + l15 * SROW + col0;
             auto half_out = [&](auto hf_tag) {
                 constexpr int HF = decltype(hf_tag)::value;
                 f32x4 acc[JH];
                 product(hf_tag, th0, th1, tl0, tl1, acc);
+                if constexpr (HF == 0) {
+                    wait();                                       // W(gq): this group's T rows, requested one group ago
+#pragma unroll
+                    for (int i = 0; i < R; ++i) landed(te[i]);
+                }
                 uint32_t oh[2 * JH];
 #pragma unroll
                 for (int jj = 0; jj < JH; ++jj) {
-                    f32x4 tv = te[HF * JH + jj];
-                    if (TH) {                                       // two packed half pairs -> four floats
-                        const f16x2_t h0 = __builtin_bit_cast(f16x2_t, __float_as_uint(tv[0])), h1 = __builtin_bit_cast(f16x2_t, __float_as_uint(tv[1]));
+                    const int j = HF * JH + jj;
+                    f32x4 tv;
+                    if (TH) {                                       // request j / 2 holds tiles 2 p, 2 p + 1: two packed half pairs -> four floats
+                        const f16x2_t h0 = __builtin_bit_cast(f16x2_t, __float_as_uint(te[TH ? j >> 1 : 0][2 * (j & 1)]));
+                        const f16x2_t h1 = __builtin_bit_cast(f16x2_t, __float_as_uint(te[TH ? j >> 1 : 0][2 * (j & 1) + 1]));
                         tv = f32x4{(float)h0[0], (float)h0[1], (float)h1[0], (float)h1[1]};
+                    } else {
+                        tv = te[TH ? 0 : j];
                     }
                     if (as_f16) {
                         oh[2 * jj] = pack_f16(acc[jj][0] * rs + tv[0], acc[jj][1] * rs + tv[1]);
@@ -1298,32 +1357,40 @@ __global__ void __launch_bounds__(512) k_kv_rows(KvRowArgs a) {
             };
             half_out(std::integral_constant<int, 0>{});
             half_out(std::integral_constant<int, 1>{});
-            __syncthreads();                                      // the 16 x N block is complete
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();                         // the 16 x N block is complete (raw: no memory drain)
+            asm volatile("" ::: "memory");
             constexpr int UPR = N / 8;                            // 16-byte units per row
 #pragma unroll
-            for (int i = 0; i < N / 256; ++i) {
-                const int u = (wid * (N / 256) + i) * 64 + lane, row = u / UPR, c16 = u - row * UPR;
+            for (int i = 0; i < S; ++i) {                         // E(gq): S stores
+                const int u = (wid * S + i) * 64 + lane, row = u / UPR, c16 = u - row * UPR;
                 const int64_t r = g * TCELLS + gq * 16 + row;
                 if (r < n_rows)
                     *reinterpret_cast<u32x4 *>(a.out + r * (2 * N) + ncol0 + c16 * 8) = *reinterpret_cast<const u32x4 *>(sb + row * SROW + c16 * 8);
             }
-            (void)valid;
         };
-        f32x4 te_a[2 * JH], te_b[2 * JH];
-        float rs_a, rs_b;
-        bool va, vb;
-        request(0, te_a, rs_a, va);
-        request(1, te_b, rs_b, vb);
-        emit(0, te_a, rs_a, va);
-        request(2, te_a, rs_a, va);
-        emit(1, te_b, rs_b, vb);
-        request(3, te_b, rs_b, vb);
-        emit(2, te_a, rs_a, va);
-        emit(3, te_b, rs_b, vb);
+        // W1..W3: newer than the awaited T(q) are E(q-1) and T(q+1)
+        auto wait_sr = [&]() { if (full) vm_wait<S + R>(); else vm_wait<R>(); };
+        request(kq[1], te_b);                                     // T1: R
+        emit(0, te_a, [&]() {
+            // W0.  In flight, oldest first: T0 R (requested before group 3 of the previous tile, or above), E3 S of the previous tile
+            // (a full one: this tile exists), stage D, meta M, T1 R.  Retires T0.
+            if (first) vm_wait<D + M + R>(); else vm_wait<S + D + M + R>();
+        });
+        request(kq[2], te_a);                                     // T2: R
+        emit(1, te_b, [&]() {
+            wait_sr();                                            // W1.  In flight: stage D, meta M, T1 R, E0 S, T2 R.  Retires stage, meta and T1.
+            meta_landed(kn, rn);
+        });
+        request(kq[3], te_b);                                     // T3: R
+        emit(2, te_a, [&]() { wait_sr(); });                      // W2.  In flight: T2 R, E1 S, T3 R.  Retires T2.
+        request(kn[0], te_a);                                     // T0 of the next tile: R, in flight across the tile boundary
+        emit(3, te_b, [&]() { wait_sr(); });                      // W3.  In flight: T3 R, E2 S, T0' R.  Retires T3.
 #pragma unroll
         for (int q = 0; q < 4; ++q) { kq[q] = kn[q]; rq[q] = rn[q]; }
         buf ^= 1;
     }
+    vm_wait<0>();                                                 // the last tile's unused stage DMA and T0' request, and the stores
 }
 
 }  // namespace bt
