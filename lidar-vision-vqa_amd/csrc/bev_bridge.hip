@@ -271,10 +271,6 @@ template <typename A> void merge_layout(A &a, MergeWs &w, int64_t m, size_t dyn_
     w.dyn = a.template take<char>(dyn_bytes);
     w.dyn_bytes = dyn_bytes;
 }
-struct SizerA {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
 }  // namespace
 
 extern "C" size_t lvq_sparse_bev_merge_workspace_bytes(int64_t m, int batch, int ny, int nx) {
@@ -282,7 +278,7 @@ extern "C" size_t lvq_sparse_bev_merge_workspace_bytes(int64_t m, int batch, int
     const int32_t grid[3] = {ny, nx, 1};
     const size_t dyn = lvq_voxelize_dynamic_workspace_bytes(m, batch, grid, 2);
     if (dyn == 0) return 0;
-    SizerA a;
+    SizerAdapter a;
     MergeWs w;
     merge_layout(a, w, m, dyn);
     return a.s.total();

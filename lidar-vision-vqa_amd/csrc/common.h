@@ -71,6 +71,11 @@ struct LvqSizer {
     template <typename T> void take(size_t n) { off = lvq_align(off) + n * sizeof(T); }
     size_t total() const { return lvq_align(off) + 256; }
 };
+// LvqSizer behind LvqArena's take(): one `template <typename A> layout(A &, ...)` serves both the call and its *_workspace_bytes
+struct SizerAdapter {
+    LvqSizer s;
+    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
+};
 
 __device__ __forceinline__ float bf16_to_f32(uint16_t h) { return __uint_as_float(((uint32_t)h) << 16); }
 // round-to-nearest-even fp32 -> bf16; NaN stays NaN (MI355X_MICROARCH "Correctness boundaries")

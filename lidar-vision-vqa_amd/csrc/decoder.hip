@@ -44,10 +44,6 @@ template <typename A> void step_layout(A &a, StepWs &w, int batch, int d, int dk
     w.attn_bytes = attn_bytes;
     w.kv_len = ragged ? a.template take<int32_t>(seqs ? (size_t)seqs * 4 : (size_t)batch) : nullptr;
 }
-struct SizerA {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
 
 // lvq_qwen2_extend_shared: the sequences of the step continue shared prefixes (decode_shared.hip)
 struct SharedStep {
@@ -148,7 +144,7 @@ extern "C" size_t lvq_qwen2_decode_workspace_bytes(int batch, int d, int n_heads
     if (batch <= 0 || d <= 0 || n_heads <= 0 || n_kv_heads <= 0 || d % n_heads || inter <= 0 || lmax <= 0) return 0;
     const int dh = d / n_heads;
     const size_t attn = lvq_attention_workspace_bytes(batch, n_heads, 1, lmax, dh, precision);
-    SizerA a;
+    SizerAdapter a;
     StepWs w;
     step_layout(a, w, batch, d, dh * n_kv_heads, inter, attn);
     return a.s.total();
@@ -169,7 +165,7 @@ extern "C" size_t lvq_qwen2_decode_ragged_workspace_bytes(int batch, int d, int 
     const int dh = d / n_heads;
     const size_t attn = lvq_attention_decode_ragged_workspace_bytes(batch, n_heads, n_kv_heads, lmax, dh, precision);
     if (attn == 0) return 0;
-    SizerA a;
+    SizerAdapter a;
     StepWs w;
     step_layout(a, w, batch, d, dh * n_kv_heads, inter, attn, true);
     return a.s.total();
@@ -193,7 +189,7 @@ extern "C" size_t lvq_qwen2_extend_shared_workspace_bytes(int batch, int lq, int
     const int dh = d / n_heads;
     const size_t attn = lvq_attention_extend_shared_workspace_bytes(batch, lq, n_heads, n_kv_heads, pmax, lown, dh, precision);
     if (attn == 0) return 0;
-    SizerA a;
+    SizerAdapter a;
     StepWs w;
     step_layout(a, w, batch * lq, d, dh * n_kv_heads, inter, attn, true, batch);
     return a.s.total();

@@ -321,10 +321,6 @@ template <typename A> void rules_layout(A &a, RulesWs &w, int64_t ncand, size_t 
     w.dyn = a.template take<char>(dyn_bytes);
     w.dyn_bytes = dyn_bytes;
 }
-struct SizerR {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
 
 // LVQ_OK and a filled geometry, or the error code of the argument check
 int rules_geom(int ndim, const int32_t *shape, int batch, const int32_t *kernel, const int32_t *stride, const int32_t *padding, int subm, RuleGeom &g) {
@@ -372,7 +368,7 @@ extern "C" size_t lvq_sparse_conv_rules_workspace_bytes(int64_t n_in, int ndim, 
     if (ncand >= (1ll << 30)) return 0;
     const size_t dyn = rules_dyn_bytes(g, ncand);
     if (dyn == 0) return 0;
-    SizerR a;
+    SizerAdapter a;
     RulesWs w;
     rules_layout(a, w, ncand, dyn);
     return a.s.total();

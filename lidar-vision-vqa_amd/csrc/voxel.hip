@@ -21,102 +21,23 @@
 //   * all scans are popcount scans of u64 words (single-workgroup for <= 32k words, 3-kernel otherwise).
 //   * divisions are IEEE fp32 (-fhip-fp32-correctly-rounded-divide-sqrt, no fast-math) so that
 //     floor((p - lo) / vs) matches the CPU bit for bit.
-#include "common.h"
+//
+// voxel_common.h holds what this file shares with voxel_binned.hip and voxel_hashed.hip: Geom and the cell rule (cell_of), find_scene,
+// popc_below, the wave / block scans, first_rank, and the declarations of the slab paths this file dispatches to.  This file owns the
+// public entry points (argument checks, path order) and the scene-offset kernel both flag-word paths use (lvq_hard_scene_offsets).
+#include "voxel_common.h"
 #include <stdlib.h>
 
-// slab-binned fast paths (voxel_binned.hip); they return LVQ_EUNSUPPORTED for shapes they do not take
-size_t lvq_binned_dynamic_workspace_bytes(int64_t n);
-int lvq_binned_voxelize_dynamic(const float *pts, int64_t n, int c, int batch_size, const float *range_host,
-                                const float *vsize_host, const int32_t *grid_host, int ndim, int32_t *unq_inv, int32_t *pt_coords,
-                                int32_t *unq_key, int32_t *unq_cnt, int32_t *coords_bzyx, int32_t *counts, void *ws, size_t ws_bytes,
-                                hipStream_t st);
-
-size_t lvq_binned_hard_workspace_bytes(int64_t n, int n_scenes);
-int lvq_binned_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t n, int n_scenes, int c, const float *range_host,
-                             const float *vsize_host, const int32_t *grid_host, int max_pts, int max_voxels, float *voxels,
-                             int32_t *coords_bzyx, int32_t *num_pts, int32_t *scene_voxel_off, void *ws, size_t ws_bytes,
-                             hipStream_t st);
-
-// hash-balanced slabs + input-order placement (voxel_hashed.hip): the default hard path
-size_t lvq_hashed_hard_workspace_bytes(int64_t n, int n_scenes);
-int lvq_hashed_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t n, int n_scenes, int c, const float *range_host,
-                             const float *vsize_host, const int32_t *grid_host, int max_pts, int max_voxels, float *voxels,
-                             int32_t *coords_bzyx, int32_t *num_pts, int32_t *scene_voxel_off, void *ws, size_t ws_bytes,
-                             hipStream_t st);
-
-int lvq_hashed_voxelize_mean(const float *pts, const int32_t *scene_off, int64_t n, int n_scenes, int c, const float *range_host,
-                             const float *vsize_host, const int32_t *grid_host, int max_pts, int max_voxels, float *voxel_features,
-                             int32_t *coords_bzyx, int32_t *num_pts, int32_t *scene_voxel_off, void *ws, size_t ws_bytes,
-                             hipStream_t st);
-
 namespace {
-
-struct Geom {
-    float lo[3];
-    float vs[3];
-    int grid[3];
-};
-
-__device__ __forceinline__ bool cell_of(const float *p, const Geom &g, int ndim, int cc[3]) {
-    bool ok = true;
-    cc[0] = cc[1] = cc[2] = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        if (j < ndim) {
-            float d = p[j] - g.lo[j];
-            float q = d / g.vs[j];
-            float f = floorf(q);
-            bool in = (f >= 0.0f) && (f < (float)g.grid[j]);  // NaN/inf fail here like (int) casts do on the CPU
-            ok = ok && in;
-            cc[j] = in ? (int)f : -1;
-        }
-    }
-    return ok;
-}
-
-__device__ __forceinline__ int find_scene(const int32_t *off, int n_scenes, int i) {
-    int lo = 0, hi = n_scenes;  // largest s with off[s] <= i
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
 
 __device__ __forceinline__ uint32_t mix64(uint64_t k) {
     k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
     return (uint32_t)k;
 }
 
-__device__ __forceinline__ int popc_below(uint64_t m, int bit) {
-    return __popcll(m & ((bit == 0) ? 0ull : (~0ull >> (64 - bit))));
-}
-
 // ---------------------------------------------------------------------------------------------
 // popcount scans
 // ---------------------------------------------------------------------------------------------
-// block-wide exclusive scan of one int per thread (blockDim.x multiple of 64, <= 1024)
-__device__ __forceinline__ int block_excl_scan(int v, int *lds_wave_tot, int &block_total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) lds_wave_tot[wid] = incl;
-    __syncthreads();
-    int wbase = 0, tot = 0;
-    for (int w = 0; w < nw; ++w) {
-        int t = lds_wave_tot[w];
-        if (w < wid) wbase += t;
-        tot += t;
-    }
-    __syncthreads();
-    block_total = tot;
-    return wbase + incl - v;
-}
-
 // prefix[w] = sum_{u<w} popc(words[u]) for w in [0, nwords]; single workgroup, any length
 __global__ void __launch_bounds__(1024) k_scan_popc_single(const uint64_t *__restrict__ words, int64_t nwords,
                                                             int32_t *__restrict__ prefix, int32_t *total_out) {
@@ -126,7 +47,7 @@ __global__ void __launch_bounds__(1024) k_scan_popc_single(const uint64_t *__res
         int64_t w = base + threadIdx.x;
         int v = (w < nwords) ? __popcll(words[w]) : 0;
         int tot;
-        int ex = block_excl_scan(v, wave_tot, tot);
+        int ex = block_excl_scan(v, wave_tot, 16, tot);
         if (w < nwords) prefix[w] = running + ex;
         running += tot;
     }
@@ -162,7 +83,7 @@ __global__ void __launch_bounds__(1024) k_scan_tiles(int32_t *tsum, int nt, int3
         int t = base + threadIdx.x;
         int v = (t < nt) ? tsum[t] : 0;
         int tot;
-        int ex = block_excl_scan(v, wave_tot, tot);
+        int ex = block_excl_scan(v, wave_tot, 16, tot);
         if (t < nt) tsum[t] = running + ex;
         running += tot;
     }
@@ -189,7 +110,7 @@ __global__ void __launch_bounds__(256) k_scan_popc_apply(const uint64_t *__restr
         s += v[j];
     }
     int tot;
-    int ex = block_excl_scan(s, wave_tot, tot) + running;
+    int ex = block_excl_scan(s, wave_tot, 4, tot) + running;
 #pragma unroll
     for (int j = 0; j < 16; ++j) {
         int64_t w = w0 + j;
@@ -202,6 +123,7 @@ __global__ void __launch_bounds__(256) k_scan_popc_apply(const uint64_t *__restr
 // prefix must hold nwords+1 ints, tsum ceil(nwords/SCAN_TILE)+1 ints
 void scan_popc(const uint64_t *words, int64_t nwords, int32_t *prefix, int32_t *tsum, int32_t *total_out,
                hipStream_t st) {
+    // block sizes here are tied to the wave counts the kernels hand to block_excl_scan: 1024 threads = 16 waves, 256 threads = 4 waves
     if (nwords <= 32768) {
         hipLaunchKernelGGL(k_scan_popc_single, dim3(1), dim3(1024), 0, st, words, nwords, prefix, total_out);
         return;
@@ -296,6 +218,7 @@ __global__ void __launch_bounds__(256) k_hard_flags(int n, HardWs w) {
     if ((threadIdx.x & 63) == 0 && i < n) w.fmask[i >> 6] = m;
     // bucket allocation: ONE atomic per wave (a per-point atomicAdd on the single cursor serialised ~0.2 ns each:
     // 104 us for 485k voxels); wave-level exclusive scan of the counts, lane 63 fetches the base
+    // (the ladder of wave_incl_scan, voxel_common.h, written out: through the helper this kernel compiles to one VGPR more)
     const int lane = threadIdx.x & 63;
     int cnt = isf ? w.count[sl] : 0;
     int incl = cnt;
@@ -311,20 +234,22 @@ __global__ void __launch_bounds__(256) k_hard_flags(int n, HardWs w) {
     if (isf) w.bstart[sl] = base + incl - cnt;
 }
 
-__device__ __forceinline__ int first_rank(const HardWs &w, int i) {
-    return w.wprefix[i >> 6] + popc_below(w.fmask[i >> 6], i & 63);
-}
-
-// per scene: global rank at scene start, voxel totals, packed output offsets
-__global__ void k_hard_scene_offsets(const int32_t *__restrict__ scene_off, int n_scenes, int max_voxels, HardWs w,
-                                     int32_t *__restrict__ scene_voxel_off) {
-    for (int s = threadIdx.x; s <= n_scenes; s += blockDim.x) w.sfr[s] = first_rank(w, scene_off[s]);
+// per scene: global first-rank at the scene start, voxel totals, packed output offsets (behind lvq_hard_scene_offsets: the hard path
+// of voxel_binned.hip launches it too).  A scene start at or past nwords * 64 (the end of the cloud when its size is a multiple of 64)
+// takes wpre[nwords], the total, and does not read fmask[nwords], which only this file's path initialises.
+__global__ void k_hard_scene_offsets(const int32_t *__restrict__ scene_off, int n_scenes, int nwords, int max_voxels,
+                                     const uint64_t *__restrict__ fmask, const int32_t *__restrict__ wpre,
+                                     int32_t *__restrict__ sfr, int32_t *__restrict__ scene_voxel_off) {
+    for (int s = threadIdx.x; s <= n_scenes; s += blockDim.x) {
+        const int i = scene_off[s];
+        sfr[s] = (i >> 6) < nwords ? first_rank(fmask, wpre, i) : wpre[nwords];
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         int acc = 0;
         for (int s = 0; s < n_scenes; ++s) {
             scene_voxel_off[s] = acc;
-            int tot = w.sfr[s + 1] - w.sfr[s];
+            const int tot = sfr[s + 1] - sfr[s];
             acc += tot < max_voxels ? tot : max_voxels;
         }
         scene_voxel_off[n_scenes] = acc;
@@ -342,7 +267,7 @@ __global__ void __launch_bounds__(256) k_hard_assign(const float *__restrict__ p
     if (sl < 0) return;
     if (w.first[sl] == i) {
         int s = find_scene(scene_off, n_scenes, i);
-        int r = first_rank(w, i) - w.sfr[s];
+        int r = first_rank(w.fmask, w.wprefix, i) - w.sfr[s];
         if (r < max_voxels) {
             int v = scene_voxel_off[s] + r;
             w.vid[sl] = v;
@@ -436,11 +361,6 @@ template <typename A> void hard_layout(A &a, HardWs &w, int64_t n, int n_scenes)
     w.limit = a.template take<int32_t>(n_scenes);
     w.cursor = a.template take<int32_t>(4);
 }
-
-struct SizerAdapter {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
 
 // ---------------------------------------------------------------------------------------------
 // dynamic voxeliser
@@ -555,6 +475,12 @@ __global__ void __launch_bounds__(256) k_dyn_rank(int n, Geom g, int ndim, DynWs
 
 }  // namespace
 
+void lvq_hard_scene_offsets(const int32_t *scene_off, int n_scenes, int nwords, int max_voxels, const uint64_t *fmask,
+                            const int32_t *wpre, int32_t *sfr, int32_t *scene_voxel_off, hipStream_t st) {
+    hipLaunchKernelGGL(k_hard_scene_offsets, dim3(1), dim3(256), 0, st, scene_off, n_scenes, nwords, max_voxels, fmask, wpre, sfr,
+                       scene_voxel_off);
+}
+
 // =================================================================================================
 // C ABI
 // =================================================================================================
@@ -579,26 +505,40 @@ extern "C" size_t lvq_voxelize_hard_workspace_bytes(int64_t n_points, int n_scen
     return need;
 }
 
+// Argument checks of lvq_voxelize_hard and lvq_voxelize_mean, in the order tests/test_abi.py pins; `out` is voxels / voxel_features and
+// max_points the first point count the entry refuses as LVQ_EUNSUPPORTED.  Returns HARD_ARGS_GO_ON when the caller should launch, else
+// the call's return code (n_points == 0 is complete here: only scene_voxel_off is written).
+constexpr int HARD_ARGS_GO_ON = 1;
+static int hard_args(const float *pts, const int32_t *scene_off, int64_t n_points, int n_scenes, int c, const float *range_host,
+                     const float *vsize_host, const int32_t *grid_host, int max_pts, int max_voxels, int64_t max_points,
+                     int64_t voxel_capacity, const float *out, const int32_t *coords_bzyx, const int32_t *num_pts,
+                     int32_t *scene_voxel_off, const void *ws, size_t ws_bytes, hipStream_t st) {
+    if (n_points < 0 || n_scenes <= 0 || c < 3 || max_pts <= 0 || max_voxels <= 0 || !range_host || !vsize_host ||
+        !grid_host || !scene_off || !scene_voxel_off)
+        return LVQ_EINVAL;
+    if (n_points >= max_points) return LVQ_EUNSUPPORTED;
+    for (int j = 0; j < 3; ++j)
+        if (grid_host[j] <= 0 || !(vsize_host[j] > 0.f)) return LVQ_EINVAL;
+    if (n_points == 0) {
+        hipMemsetAsync(scene_voxel_off, 0, sizeof(int32_t) * (n_scenes + 1), st);
+        return lvq_launch_status();
+    }
+    const int64_t need = n_points < (int64_t)n_scenes * max_voxels ? n_points : (int64_t)n_scenes * max_voxels;
+    if (voxel_capacity < need || !pts || !out || !coords_bzyx || !num_pts) return LVQ_EINVAL;
+    // the contract is the QUERIED size (whichever implementation ends up running): checked before anything is launched
+    if (!ws || ws_bytes < lvq_voxelize_hard_workspace_bytes(n_points, n_scenes)) return LVQ_EWORKSPACE;
+    return HARD_ARGS_GO_ON;
+}
+
 extern "C" int lvq_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t n_points, int n_scenes, int c,
                                  const float *range_host, const float *vsize_host, const int32_t *grid_host,
                                  int max_pts, int max_voxels, int break_on_cap, int64_t voxel_capacity,
                                  float *voxels, int32_t *coords_bzyx, int32_t *num_pts, int32_t *scene_voxel_off,
                                  void *ws, size_t ws_bytes, lvq_stream_t stream) {
-    if (n_points < 0 || n_scenes <= 0 || c < 3 || max_pts <= 0 || max_voxels <= 0 || !range_host || !vsize_host ||
-        !grid_host || !scene_off || !scene_voxel_off)
-        return LVQ_EINVAL;
-    if (n_points >= (1ll << 30)) return LVQ_EUNSUPPORTED;
-    for (int j = 0; j < 3; ++j)
-        if (grid_host[j] <= 0 || !(vsize_host[j] > 0.f)) return LVQ_EINVAL;
     hipStream_t st = lvq_s(stream);
-    if (n_points == 0) {
-        hipMemsetAsync(scene_voxel_off, 0, sizeof(int32_t) * (n_scenes + 1), st);
-        return lvq_launch_status();
-    }
-    int64_t need = n_points < (int64_t)n_scenes * max_voxels ? n_points : (int64_t)n_scenes * max_voxels;
-    if (voxel_capacity < need || !pts || !voxels || !coords_bzyx || !num_pts) return LVQ_EINVAL;
-    // the contract is the QUERIED size (whichever implementation ends up running): checked before anything is launched
-    if (!ws || ws_bytes < lvq_voxelize_hard_workspace_bytes(n_points, n_scenes)) return LVQ_EWORKSPACE;
+    const int args = hard_args(pts, scene_off, n_points, n_scenes, c, range_host, vsize_host, grid_host, max_pts, max_voxels, 1ll << 30,
+                               voxel_capacity, voxels, coords_bzyx, num_pts, scene_voxel_off, ws, ws_bytes, st);
+    if (args != HARD_ARGS_GO_ON) return args;
     // default: hash-balanced slabs (voxel_hashed.hip); shapes it does not take go to the slab-binned path, then to the
     // global-hash kernels below.  LVQ_VOXEL_BINNED / LVQ_VOXEL_LEGACY force the older paths (tests, A/B timing).
     if (!break_on_cap && lvq_tune().voxel_path == 0) {
@@ -615,8 +555,7 @@ extern "C" int lvq_voxelize_hard(const float *pts, const int32_t *scene_off, int
     HardWs w;
     hard_layout(arena, w, n_points, n_scenes);
     if (!arena.ok) return LVQ_EWORKSPACE;
-    Geom g;
-    for (int j = 0; j < 3; ++j) { g.lo[j] = range_host[j]; g.vs[j] = vsize_host[j]; g.grid[j] = grid_host[j]; }
+    const Geom g = make_geom(range_host, vsize_host, grid_host);
     const int n = (int)n_points;
     const uint32_t cap = hard_cap(n_points);
     const int64_t nwords = lvq_cdiv(n_points, 64);
@@ -628,8 +567,7 @@ extern "C" int lvq_voxelize_hard(const float *pts, const int32_t *scene_off, int
     else    hipLaunchKernelGGL(k_hard_insert<0>, dim3(nb), dim3(256), 0, st, pts, scene_off, n, n_scenes, c, g, cap - 1, w);
     hipLaunchKernelGGL(k_hard_flags, dim3(nb), dim3(256), 0, st, n, w);
     scan_popc(w.fmask, nwords + 1, w.wprefix, w.tsum, nullptr, st);
-    hipLaunchKernelGGL(k_hard_scene_offsets, dim3(1), dim3(256), 0, st, scene_off, n_scenes, max_voxels, w,
-                       scene_voxel_off);
+    lvq_hard_scene_offsets(scene_off, n_scenes, (int)nwords, max_voxels, w.fmask, w.wprefix, w.sfr, scene_voxel_off, st);
     if (c4) {
         hipLaunchKernelGGL(k_hard_assign<1>, dim3(nb), dim3(256), 0, st, pts, scene_off, n, n_scenes, c, g, max_voxels, w,
                            scene_voxel_off, coords_bzyx);
@@ -651,19 +589,11 @@ extern "C" int lvq_voxelize_mean(const float *pts, const int32_t *scene_off, int
                                  const float *range_host, const float *vsize_host, const int32_t *grid_host, int max_pts,
                                  int max_voxels, int64_t voxel_capacity, float *voxel_features, int32_t *coords_bzyx,
                                  int32_t *num_pts, int32_t *scene_voxel_off, void *ws, size_t ws_bytes, lvq_stream_t stream) {
-    if (n_points < 0 || n_scenes <= 0 || c < 3 || max_pts <= 0 || max_voxels <= 0 || !range_host || !vsize_host || !grid_host ||
-        !scene_off || !scene_voxel_off)
-        return LVQ_EINVAL;
-    for (int j = 0; j < 3; ++j)
-        if (grid_host[j] <= 0 || !(vsize_host[j] > 0.f)) return LVQ_EINVAL;
     hipStream_t st = lvq_s(stream);
-    if (n_points == 0) {
-        hipMemsetAsync(scene_voxel_off, 0, sizeof(int32_t) * (n_scenes + 1), st);
-        return lvq_launch_status();
-    }
-    const int64_t need = n_points < (int64_t)n_scenes * max_voxels ? n_points : (int64_t)n_scenes * max_voxels;
-    if (voxel_capacity < need || !pts || !voxel_features || !coords_bzyx || !num_pts) return LVQ_EINVAL;
-    if (!ws || ws_bytes < lvq_voxelize_hard_workspace_bytes(n_points, n_scenes)) return LVQ_EWORKSPACE;
+    // (no point limit of its own: the hashed path refuses what it does not take after these checks)
+    const int args = hard_args(pts, scene_off, n_points, n_scenes, c, range_host, vsize_host, grid_host, max_pts, max_voxels, INT64_MAX,
+                               voxel_capacity, voxel_features, coords_bzyx, num_pts, scene_voxel_off, ws, ws_bytes, st);
+    if (args != HARD_ARGS_GO_ON) return args;
     return lvq_hashed_voxelize_mean(pts, scene_off, n_points, n_scenes, c, range_host, vsize_host, grid_host, max_pts, max_voxels,
                                     voxel_features, coords_bzyx, num_pts, scene_voxel_off, ws, ws_bytes, st);
 }
@@ -720,8 +650,7 @@ extern "C" int lvq_voxelize_dynamic(const float *pts, int64_t n, int c, int batc
     DynWs w;
     dyn_layout(arena, w, n, ks);
     if (!arena.ok) return LVQ_EWORKSPACE;
-    Geom g;
-    for (int j = 0; j < 3; ++j) { g.lo[j] = range_host[j]; g.vs[j] = vsize_host[j]; g.grid[j] = grid_host[j]; }
+    const Geom g = make_geom(range_host, vsize_host, grid_host);
     const int64_t n0 = lvq_cdiv(ks, 64), n1 = lvq_cdiv(n0, 64);
     const int64_t cap = n < ks ? n : ks;
     const unsigned nb = (unsigned)lvq_cdiv(n, 256);

@@ -15,15 +15,12 @@
 //
 // Caps: a slab with more voxels than the LDS counters hold falls back to global atomics for that slab only.
 // Shapes the binned path does not take (key space > 2^30, C != 4 payloads, ...) use the voxel.hip kernels.
-#include "common.h"
+//
+// The cell rule, find_scene, popc_below, the block scan, the key decode's idiv_rcp, first_rank and the declarations of this file's
+// entry points (called from voxel.hip, which has checked the arguments) are in voxel_common.h.
+#include "voxel_common.h"
 
 namespace vb {
-
-struct Geom {
-    float lo[3];
-    float vs[3];
-    int grid[3];
-};
 
 struct BinCfg {
     int logslab;       // keys per slab = 1 << logslab
@@ -37,33 +34,12 @@ constexpr int MAX_SLABS = 8192;
 constexpr int BIN_BLOCK = 1024;         // threads
 constexpr int BIN_PPT = 4;              // points per thread
 
-__device__ __forceinline__ int find_scene(const int32_t *off, int n_scenes, int i) {
-    int lo = 0, hi = n_scenes;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // linear key of point i or -1; cc = cell coordinates (cx, cy, cz)
 __device__ __forceinline__ int64_t key_of(const float *__restrict__ pts, int i, int c, const Geom &g, const BinCfg &cfg,
                                          const int32_t *__restrict__ scene_off, int cc[3]) {
     const float *p = pts + (int64_t)i * c;
     const float *xyz = cfg.mode == 0 ? p + 1 : p;
-    bool ok = true;
-    cc[0] = cc[1] = cc[2] = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        if (j < cfg.ndim) {
-            float d = xyz[j] - g.lo[j];
-            float q = d / g.vs[j];
-            float f = floorf(q);
-            bool in = (f >= 0.0f) && (f < (float)g.grid[j]);
-            ok = ok && in;
-            cc[j] = in ? (int)f : -1;
-        }
-    }
+    bool ok = cell_of(xyz, g, cfg.ndim, cc);
     int b;
     if (cfg.mode == 0) {
         b = (int)p[0];
@@ -105,28 +81,14 @@ __global__ void __launch_bounds__(BIN_BLOCK) k_bin_hist(const float *__restrict_
 __global__ void __launch_bounds__(1024) k_scan_small(const int32_t *__restrict__ in, int n, int32_t *__restrict__ out,
                                                      int32_t *__restrict__ zero_me, int32_t *__restrict__ total_out) {
     __shared__ int wave_tot[16];
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     int running = 0;
     for (int base = 0; base < n; base += 1024) {
         const int i = base + threadIdx.x;
         const int v = i < n ? in[i] : 0;
-        int incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) wave_tot[wid] = incl;
-        __syncthreads();
-        int wbase = 0, tot = 0;
-        for (int w = 0; w < 16; ++w) {
-            const int t = wave_tot[w];
-            if (w < wid) wbase += t;
-            tot += t;
-        }
-        __syncthreads();
+        int tot;
+        const int ex = block_excl_scan(v, wave_tot, 16, tot);
         if (i < n) {
-            out[i] = running + wbase + incl - v;
+            out[i] = running + ex;
             if (zero_me) zero_me[i] = 0;
         }
         running += tot;
@@ -156,13 +118,9 @@ __global__ void __launch_bounds__(BIN_BLOCK) k_bin_scatter(const float *__restri
             const int b = threadIdx.x * per + j;
             if (b < cfg.nslabs) csum += ghist_or_null[b];
         }
+        // block_excl_scan's steps with ONE barrier: wave_tot_s is not reused, and the barrier after the histogram reset below follows
         const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        int incl = csum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (lane >= o) incl += t;
-        }
+        const int incl = wave_incl_scan(csum);
         if (lane == 63) wave_tot_s[wid] = incl;
         __syncthreads();
         int wbase = 0, tot = 0;
@@ -221,46 +179,6 @@ __global__ void __launch_bounds__(BIN_BLOCK) k_bin_scatter(const float *__restri
 
 constexpr int SLAB_NT = 1024;     // threads per slab workgroup (dense slabs set the tail; 256 threads were 2x slower)
 
-// ---- block-wide exclusive scan helper (blockDim.x = SLAB_NT) ----
-template <int NT = SLAB_NT>
-__device__ __forceinline__ int block_excl_scan256(int v, int *wave_tot, int &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    int wbase = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const int t = wave_tot[w];
-        if (w < wid) wbase += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return wbase + incl - v;
-}
-
-// floor(a / d) for 0 <= a < 2^31, d >= 1.  (The first version estimated the quotient in fp32 with one correction step each way;
-// above ~2^29 the estimate is off by more than one divisor and keys of scenes >= 12 on the 0.1 m grid decoded to wrong
-// (z, y, x) -- found by tests/test_gpu_lidar.py::test_hard_voxelizer_paths_agree_at_scale.)  The fp32 estimate is within a few
-// units of the quotient (relative error 2^-23 of a quotient < 2^26); the correction LOOPS make it exact for every a.
-__device__ __forceinline__ int fdiv(int a, int d, float rd) {
-    int q = (int)((float)a * rd);
-    int r = a - q * d;
-    while (r < 0) { --q; r += d; }
-    while (r >= d) { ++q; r -= d; }
-    return q;
-}
-
-__device__ __forceinline__ int popc_below(uint64_t m, int bit) {
-    return __popcll(m & ((bit == 0) ? 0ull : (~0ull >> (64 - bit))));
-}
-
 constexpr int DYN_NT = 512;       // threads per slab workgroup of the dynamic path (four workgroups per CU instead of two at 1024)
 // ---- dynamic pass B: occupied cells per slab ----
 __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_count(BinCfg cfg, const int32_t *__restrict__ gstart,
@@ -284,7 +202,7 @@ __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_count(BinCfg cfg, const int
     int c = 0;
     for (int w = threadIdx.x; w < nw; w += DYN_NT) c += __popcll(bm[w]);
     int tot;
-    block_excl_scan256<DYN_NT>(c, wave_tot, tot);
+    block_excl_scan(c, wave_tot, DYN_NT / 64, tot);
     if (threadIdx.x == 0) slab_cnt[s] = tot;
 }
 
@@ -310,9 +228,9 @@ __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_write(BinCfg cfg, Geom g, c
         if (b < s) before += v;
     }
     int vbase, total;
-    block_excl_scan256<DYN_NT>(before, wave_tot, vbase);
+    block_excl_scan(before, wave_tot, DYN_NT / 64, vbase);
     if (s == 0) {
-        block_excl_scan256<DYN_NT>(all, wave_tot, total);
+        block_excl_scan(all, wave_tot, DYN_NT / 64, total);
         if (threadIdx.x == 0) *m_out = total;
         if (p0 == p1) return;
     }
@@ -342,7 +260,7 @@ __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_write(BinCfg cfg, Geom g, c
         if (w < nw) c += __popcll(bm[w]);
     }
     int tot;
-    int ex = block_excl_scan256<DYN_NT>(c, wave_tot, tot);
+    int ex = block_excl_scan(c, wave_tot, DYN_NT / 64, tot);
     for (int j = 0; j < per; ++j) {
         const int w = threadIdx.x * per + j;
         if (w < nw) { wpre[w] = ex; ex += __popcll(bm[w]); }
@@ -384,11 +302,11 @@ __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_write(BinCfg cfg, Geom g, c
         const int vo = vbase + v;
         unq_key[vo] = key;
         if (lds_cnt) unq_cnt[vo] = cnt_l[v];
-        // key -> (b, cx, cy, cz) with float-reciprocal division (exact for key < 2^30 after the fix-up step)
+        // key -> (b, cx, cy, cz) with float-reciprocal division (idiv_rcp: exact for every key < 2^31)
         int bq, cx, cy, cz = 0, t = key;
-        if (cfg.ndim == 3) { const int q = fdiv(t, g.grid[2], rz); cz = t - q * g.grid[2]; t = q; }
-        { const int q = fdiv(t, g.grid[1], ry); cy = t - q * g.grid[1]; t = q; }
-        { const int q = fdiv(t, g.grid[0], rx); cx = t - q * g.grid[0]; bq = q; }
+        if (cfg.ndim == 3) { const int q = idiv_rcp(t, g.grid[2], rz); cz = t - q * g.grid[2]; t = q; }
+        { const int q = idiv_rcp(t, g.grid[1], ry); cy = t - q * g.grid[1]; t = q; }
+        { const int q = idiv_rcp(t, g.grid[0], rx); cx = t - q * g.grid[0]; bq = q; }
         reinterpret_cast<int4 *>(coords_bzyx)[vo] = make_int4(bq, cz, cy, cx);
     }
 }
@@ -423,11 +341,6 @@ template <typename A> void dyn_layout(A &a, DynBinWs &w, int64_t n) {
     w.sidx = a.template take<int32_t>(n + 1);
     w.soff = a.template take<int32_t>(n + 1);
 }
-
-struct SizerAdapter {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
 
 // =================================================================================================================
 // hard voxeliser on the same binning pass
@@ -540,7 +453,7 @@ __global__ void __launch_bounds__(SLAB_NT) k_hard_slab(BinCfg cfg, int T, HardBi
         if (x < nw) c += __popcll(bm[x]);
     }
     int nvox;
-    int ex = block_excl_scan256(c, wave_tot, nvox);
+    int ex = block_excl_scan(c, wave_tot, SLAB_NT / 64, nvox);
     for (int j = 0; j < per; ++j) {
         const int x = tid * per + j;
         if (x < nw) { wpre[x] = ex; ex += __popcll(bm[x]); }
@@ -571,7 +484,7 @@ __global__ void __launch_bounds__(SLAB_NT) k_hard_slab(BinCfg cfg, int T, HardBi
         const int v = base + tid;
         const int x = v < nvox ? cnt[v] : 0;
         int tot;
-        const int e2 = block_excl_scan256(x, wave_tot, tot);
+        const int e2 = block_excl_scan(x, wave_tot, SLAB_NT / 64, tot);
         if (v < nvox) vstart[v] = running + e2;
         running += tot;
     }
@@ -615,29 +528,6 @@ __global__ void __launch_bounds__(256) k_flags_to_words(const uint8_t *__restric
     if ((threadIdx.x & 63) == 0 && i < n) { fmask[i >> 6] = m; wcnt[i >> 6] = __popcll(m); }
 }
 
-__device__ __forceinline__ int first_rank(const HardBinWs &w, int i) {
-    return w.wpre[i >> 6] + popc_below(w.fmask[i >> 6], i & 63);
-}
-
-__global__ void k_hard_scene_offsets2(const int32_t *__restrict__ scene_off, int n, int n_scenes, int max_voxels, HardBinWs w,
-                                      int32_t *__restrict__ scene_voxel_off) {
-    const int nwords = (n + 63) / 64;
-    for (int s = threadIdx.x; s <= n_scenes; s += blockDim.x) {
-        const int i = scene_off[s];
-        w.sfr[s] = (i >> 6) < nwords ? first_rank(w, i) : w.wpre[nwords];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int acc = 0;
-        for (int s = 0; s < n_scenes; ++s) {
-            scene_voxel_off[s] = acc;
-            const int tot = w.sfr[s + 1] - w.sfr[s];
-            acc += tot < max_voxels ? tot : max_voxels;
-        }
-        scene_voxel_off[n_scenes] = acc;
-    }
-}
-
 // ---- hard pass C: placement, one thread per sorted position (coalesced reads, 16-byte row stores) ----
 __global__ void __launch_bounds__(256) k_hard_place(int n_sorted, BinCfg cfg, Geom g, int T, int max_voxels,
                                                     const int32_t *__restrict__ scene_off, HardBinWs w,
@@ -647,7 +537,7 @@ __global__ void __launch_bounds__(256) k_hard_place(int n_sorted, BinCfg cfg, Ge
     if (p >= n_sorted || p >= w.gstart[cfg.nslabs]) return;     // only the binned (in-range) points have sorted positions
     const int f = w.pfirst[p], r = w.pslot[p], idx = w.sidx[p];
     const int s = find_scene(scene_off, cfg.n_scenes, f);
-    const int rank = first_rank(w, f) - w.sfr[s];
+    const int rank = first_rank(w.fmask, w.wpre, f) - w.sfr[s];
     if (rank >= max_voxels) return;                       // voxel never created (`continue` semantics)
     const int v = scene_voxel_off[s] + rank;
     float4 *row = reinterpret_cast<float4 *>(voxels) + (int64_t)v * T;
@@ -667,9 +557,9 @@ __global__ void __launch_bounds__(256) k_hard_place(int n_sorted, BinCfg cfg, Ge
         const int64_t key = ((int64_t)lo << cfg.logslab) + w.soff[p];
         const float rx = 1.0f / (float)g.grid[0], ry = 1.0f / (float)g.grid[1], rz = 1.0f / (float)g.grid[2];
         int t = (int)key;
-        int q = fdiv(t, g.grid[2], rz); const int cz = t - q * g.grid[2]; t = q;
-        q = fdiv(t, g.grid[1], ry); const int cy = t - q * g.grid[1]; t = q;
-        q = fdiv(t, g.grid[0], rx); const int cx = t - q * g.grid[0];
+        int q = idiv_rcp(t, g.grid[2], rz); const int cz = t - q * g.grid[2]; t = q;
+        q = idiv_rcp(t, g.grid[1], ry); const int cy = t - q * g.grid[1]; t = q;
+        q = idiv_rcp(t, g.grid[0], rx); const int cx = t - q * g.grid[0];
         reinterpret_cast<int4 *>(coords_bzyx)[v] = make_int4(s, cz, cy, cx);
     }
 }
@@ -680,7 +570,7 @@ __global__ void __launch_bounds__(256) k_hard_place(int n_sorted, BinCfg cfg, Ge
 // entry points used by voxel.hip's lvq_voxelize_dynamic (returns LVQ_EUNSUPPORTED when the binned path does not apply)
 // -------------------------------------------------------------------------------------------------
 size_t lvq_binned_dynamic_workspace_bytes(int64_t n) {
-    vb::SizerAdapter a;
+    SizerAdapter a;
     vb::DynBinWs w;
     vb::dyn_layout(a, w, n);
     return a.s.total();
@@ -700,8 +590,7 @@ int lvq_binned_voxelize_dynamic(const float *pts, int64_t n, int c, int batch_si
     DynBinWs w;
     dyn_layout(arena, w, n);
     if (!arena.ok) return LVQ_EWORKSPACE;
-    Geom g;
-    for (int j = 0; j < 3; ++j) { g.lo[j] = range_host[j]; g.vs[j] = vsize_host[j]; g.grid[j] = grid_host[j]; }
+    const Geom g = make_geom(range_host, vsize_host, grid_host);
     const unsigned nb = (unsigned)lvq_cdiv(n, BIN_BLOCK * BIN_PPT);
     const int64_t cap = n < keyspace ? n : keyspace;
     hipMemsetAsync(w.ghist, 0, sizeof(int32_t) * 2 * (MAX_SLABS + 64), st);      // histogram + cursors (contiguous)
@@ -722,7 +611,7 @@ int lvq_binned_voxelize_dynamic(const float *pts, int64_t n, int c, int batch_si
 }
 
 size_t lvq_binned_hard_workspace_bytes(int64_t n, int n_scenes) {
-    vb::SizerAdapter a;
+    SizerAdapter a;
     vb::HardBinWs w;
     vb::hard_layout(a, w, n, n_scenes);
     return a.s.total();
@@ -743,8 +632,7 @@ int lvq_binned_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t
     HardBinWs w;
     hard_layout(arena, w, n, n_scenes);
     if (!arena.ok) return LVQ_EWORKSPACE;
-    Geom g;
-    for (int j = 0; j < 3; ++j) { g.lo[j] = range_host[j]; g.vs[j] = vsize_host[j]; g.grid[j] = grid_host[j]; }
+    const Geom g = make_geom(range_host, vsize_host, grid_host);
     const unsigned nb = (unsigned)lvq_cdiv(n, BIN_BLOCK * BIN_PPT);
     const int64_t nwords = (n + 63) / 64;
     hipMemsetAsync(w.ghist, 0, sizeof(int32_t) * (cfg.nslabs + 1), st);
@@ -763,7 +651,7 @@ int lvq_binned_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t
     hipLaunchKernelGGL(k_flags_to_words, dim3((unsigned)lvq_cdiv(nwords * 64, 256)), dim3(256), 0, st, w.fbytes, (int)(nwords * 64), w.fmask,
                        w.wcnt);
     hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, st, w.wcnt, (int)nwords, w.wpre, (int32_t *)nullptr, (int32_t *)nullptr);
-    hipLaunchKernelGGL(k_hard_scene_offsets2, dim3(1), dim3(256), 0, st, scene_off, (int)n, n_scenes, max_voxels, w, scene_voxel_off);
+    lvq_hard_scene_offsets(scene_off, n_scenes, (int)nwords, max_voxels, w.fmask, w.wpre, w.sfr, scene_voxel_off, st);
     // the number of binned (valid) points is only known on the device (gstart[nslabs]); launch over n and let extra threads exit
     hipLaunchKernelGGL(k_hard_place, dim3((unsigned)lvq_cdiv(n, 256)), dim3(256), 0, st, (int)n, cfg, g, max_pts, max_voxels, scene_off, w,
                        scene_voxel_off, voxels, coords_bzyx, num_pts);

@@ -31,15 +31,12 @@
 //   why the count of operations was the first thing to cut).
 //   Unsupported shapes (C != 4, T > 127, key space >= 2^31, N > 4 M, > 1024 scenes, `break` cap) -> LVQ_EUNSUPPORTED
 //   and the caller falls back to voxel_binned.hip / the hash kernels in voxel.hip.
-#include "common.h"
+//
+// The cell rule, find_scene, popc_below, the wave / block scans, idiv_rcp_small and the declarations of this file's entry points
+// (called from voxel.hip, which has checked the arguments) are in voxel_common.h.
+#include "voxel_common.h"
 
 namespace vh {
-
-struct Geom {
-    float lo[3];
-    float vs[3];
-    int grid[3];
-};
 
 constexpr int MAX_SLABS = 4096;
 constexpr int BIN_NT = 1024;          // threads of a binning block
@@ -97,36 +94,6 @@ template <typename A> void layout(A &a, Ws &w, int64_t n, int n_scenes) {
     w.g_start = a.template take<int32_t>(2 * n + 64);
 }
 
-struct SizerAdapter {
-    LvqSizer s;
-    template <typename T> T *take(size_t n) { s.template take<T>(n); return nullptr; }
-};
-
-__device__ __forceinline__ int find_scene(const int32_t *off, int n_scenes, int i) {
-    int lo = 0, hi = n_scenes;
-    while (hi - lo > 1) {
-        int mid = (lo + hi) >> 1;
-        if (off[mid] <= i) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// cell coordinates (cx, cy, cz) of a point: floor((p - lo) / vs) in IEEE fp32, in-range test as the reference does it
-__device__ __forceinline__ bool cell_of(float x, float y, float z, const Geom &g, int cc[3]) {
-    const float p[3] = {x, y, z};
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float d = p[j] - g.lo[j];
-        const float q = d / g.vs[j];
-        const float f = floorf(q);
-        const bool in = (f >= 0.0f) && (f < (float)g.grid[j]);
-        ok = ok && in;
-        cc[j] = in ? (int)f : -1;
-    }
-    return ok;
-}
-
 // bijective 32-bit mix (odd multiplies and xor-shifts); mix(0) == 0, and keys enter as key + 1, so a mixed key is never 0
 __device__ __forceinline__ uint32_t mix32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352du;
@@ -137,31 +104,11 @@ __device__ __forceinline__ uint32_t mix32(uint32_t x) {
 
 // mixed key of point i, 0 for a point outside the grid
 __device__ __forceinline__ uint32_t mixed_key(const float4 p, int scene, const Geom &g) {
+    const float xyz[3] = {p.x, p.y, p.z};
     int cc[3];
-    if (!cell_of(p.x, p.y, p.z, g, cc)) return 0u;
+    if (!cell_of(xyz, g, 3, cc)) return 0u;
     const uint32_t key = (uint32_t)(((scene * g.grid[0] + cc[0]) * g.grid[1] + cc[1]) * g.grid[2] + cc[2]);   // < 2^31 (host check)
     return mix32(key + 1u);
-}
-
-__device__ __forceinline__ int block_excl_scan(int v, int *wave_tot, int nwaves, int &total) {
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o);
-        if (lane >= o) incl += t;
-    }
-    if (lane == 63) wave_tot[wid] = incl;
-    __syncthreads();
-    int wbase = 0, tot = 0;
-    for (int w = 0; w < nwaves; ++w) {
-        const int t = wave_tot[w];
-        if (w < wid) wbase += t;
-        tot += t;
-    }
-    __syncthreads();
-    total = tot;
-    return wbase + incl - v;
 }
 
 // ---- K1: single-pass binning.  Hash-balanced slabs need no histogram pass: every slab owns a fixed region of SLAB_CAP
@@ -468,29 +415,11 @@ __global__ void __launch_bounds__(WORDS_NT) k_words(int n, Ws w) {
     __syncthreads();
     if (tid < 64) {
         const int c = lcnt[tid];
-        int incl = c;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o);
-            if (tid >= o) incl += t;
-        }
+        const int incl = wave_incl_scan(c);
         const int wi = blockIdx.x * 64 + tid;
         if (wi < nwords) w.wloc[wi] = incl - c;
         if (tid == 63) w.btot[blockIdx.x] = incl;
     }
-}
-
-__device__ __forceinline__ int popc_below(unsigned long long m, int bit) {
-    return __popcll(m & (bit == 0 ? 0ull : (~0ull >> (64 - bit))));
-}
-
-// floor(a / d) for 0 <= a < 2^23, d >= 1
-__device__ __forceinline__ int fdiv(int a, int d, float rd) {
-    int q = (int)((float)a * rd);
-    int r = a - q * d;
-    if (r < 0) { --q; r += d; }
-    if (r >= d) ++q;
-    return q;
 }
 
 // ---- K5: placement in input order.  A wave = 64 consecutive points = one flag word.
@@ -548,7 +477,8 @@ __global__ void __launch_bounds__(PLACE_NT) k_place(const float4 *__restrict__ p
     bool inr = false;
     if (live) {
         s = find_scene(scene_off, n_scenes, i);
-        inr = cell_of(p.x, p.y, p.z, g, cc);
+        const float xyz[3] = {p.x, p.y, p.z};
+        inr = cell_of(xyz, g, 3, cc);
     }
     const bool first = fbv > 0;
     const unsigned long long fm = __ballot(first);
@@ -572,9 +502,9 @@ __global__ void __launch_bounds__(PLACE_NT) k_place(const float4 *__restrict__ p
         const int v0 = __shfl(v, __builtin_ctzll(km));                // kept first points of a wave own consecutive rows
         float4 *dst = voxels + (int64_t)v0 * T;
         const float rT = 1.0f / (float)T;
-        const int total = nk * T;
+        const int total = nk * T;                                     // nk <= 64 rows, T <= 127 (host check): e < 64 * 127 = 8128 < 2^23
         for (int e = lane; e < total; e += 64) {
-            const int row = fdiv(e, T, rT), slot = e - row * T;
+            const int row = idiv_rcp_small(e, T, rT), slot = e - row * T;
             // (non-temporal stores were tried here: 57 instead of 53 us for the call -- the plain stores combine better in L2)
             if (slot == 0) dst[e] = l_pt[wv][row];
             else if (slot >= l_np[wv][row]) dst[e] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -637,8 +567,9 @@ __global__ void __launch_bounds__(PLACE_NT) k_place_mean(const float4 *__restric
     }
     if (fbv == 0) return;                                            // only first points write
     const int s = find_scene(scene_off, n_scenes, i);
+    const float xyz[3] = {p.x, p.y, p.z};
     int cc[3];
-    cell_of(p.x, p.y, p.z, g, cc);
+    cell_of(xyz, g, 3, cc);
     const unsigned long long fm = __ballot(true);                     // the first points of this wave (all others have left)
     const int wi = (blockIdx.x * PLACE_NT + wv * 64) >> 6;
     const int rs = bpre[wi >> 6] + w.wloc[wi] + popc_below(fm, lane) - l_sfr[s];
@@ -654,7 +585,7 @@ __global__ void __launch_bounds__(PLACE_NT) k_place_mean(const float4 *__restric
 }  // namespace vh
 
 size_t lvq_hashed_hard_workspace_bytes(int64_t n, int n_scenes) {
-    vh::SizerAdapter a;
+    SizerAdapter a;
     vh::Ws w;
     vh::layout(a, w, n, n_scenes);
     return a.s.total();
@@ -679,8 +610,7 @@ static int hashed_voxelize(bool mean, const float *pts, const int32_t *scene_off
     Ws w;
     layout(arena, w, n, n_scenes);
     if (!arena.ok) return LVQ_EWORKSPACE;
-    Geom g;
-    for (int j = 0; j < 3; ++j) { g.lo[j] = range_host[j]; g.vs[j] = vsize_host[j]; g.grid[j] = grid_host[j]; }
+    const Geom g = make_geom(range_host, vsize_host, grid_host);
     static LvqLdsOnce once;
     if (!lvq_ensure_lds(once, {(const void *)k_slab<false>, (const void *)k_slab<true>}, 96 * 1024)) return LVQ_ELAUNCH;
     const unsigned nb = (unsigned)lvq_cdiv(n, BIN_NT * BIN_PPT);

@@ -1,6 +1,8 @@
 """GPU parity tests, LiDAR side: the HIP path (through the C ABI) vs the CPU oracle on the same seeded
 inputs, vs the committed goldens of the imported reference, and size-independent properties at the
 BASELINE sizes.  Integer outputs (voxel indices, counts, inverse maps) must be BIT-EXACT."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -277,13 +279,24 @@ def test_dynamic_voxelize_vs_oracle(dist, n, seed, bs, ndim, vs):
     assert np.array_equal(dv["pt_coords"].cpu().numpy()[o["keep"]][:, :ndim], o["coords"][:, :ndim])
 
 
-def test_dynamic_voxelize_16_scenes_large_keys():
-    """Keys above 2^29 (scene index >= 12 on the 0.1 m grid): the key -> (b, z, y, x) decode must stay exact."""
-    bs = 16
-    scenes = [masked("C", 20000, 300 + i) for i in range(bs)]
+@functools.lru_cache(maxsize=None)
+def large_keys_case():
+    """16 scenes x 20 000 points on the 1024 x 1024 x 40 grid and the oracle's result, computed once for both paths."""
+    scenes = [masked("C", 20000, 300 + i) for i in range(16)]
     pts = np.concatenate([np.concatenate((np.full((len(s), 1), i, np.float32), s), axis=1) for i, s in enumerate(scenes)])
     grid = [1024, 1024, 40]
-    o = LO.dynamic_voxelize(pts, RNG, synth.VOXEL_01, grid, 3)
+    return pts, grid, LO.dynamic_voxelize(pts, RNG, synth.VOXEL_01, grid, 3)
+
+
+# the dynamic voxeliser takes the slab-binned kernels unless voxel_path == 2 selects the two-level bitmap
+@pytest.mark.parametrize("voxel_path", [pytest.param(0, id="binned"), pytest.param(2, id="bitmap")])
+def test_dynamic_voxelize_16_scenes_large_keys(voxel_path, tune):
+    """Keys above 2^29 (scene index >= 12 on the 0.1 m grid): the key -> (b, z, y, x) decode must stay exact.  On the bitmap path the
+    163 840 level-1 words and the ~320 000 level-0 words are both above 32 768: the only case that reaches the three-kernel tiled
+    popcount scan (k_scan_popc_tilesum, k_scan_tiles, k_scan_popc_apply)."""
+    tune(voxel_path=voxel_path)
+    bs = 16
+    pts, grid, o = large_keys_case()
     dv = L()._dynamic_voxelize(torch.from_numpy(pts).to(DEV), bs, RNG, synth.VOXEL_01, grid, 3)
     m = int(dv["counts"][0])
     assert m == len(o["unq_key"]) and int(o["unq_key"].max()) > 2 ** 29
