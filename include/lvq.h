@@ -68,7 +68,8 @@ typedef struct lvq_tuning {
     int32_t pairs_one_wg;            /* 1: lvq_bev_scene_pairs with one workgroup per scene */
     int32_t ca_fused_variant;        /* diagnostics builds (CA_DEBUG_VARIANTS) only: timing-ablation variant of k_ca_fused; results are wrong */
     uint64_t ca_fused_stamps;        /* diagnostics: device pointer to [workgroups][4][8] uint64 that k_ca_fused fills with s_memrealtime stamps, or 0 */
-    int32_t reserved[8];
+    int32_t conv_rows_grid;          /* test hook: workgroups of k_conv_rows (two-launch lvq_bev_tile_kv): 0 built-in grid, n > 0 at most n */
+    int32_t reserved[7];
 } lvq_tuning;
 void lvq_tuning_defaults(lvq_tuning *t);
 int lvq_set_tuning(const lvq_tuning *t);      /* NULL restores the defaults */

@@ -946,202 +946,17 @@ struct ConvArgs {
     int32_t *key;                 // out: [dirty rows] the cell's row in the table T (tile-major key index)
 };
 
-template <bool X3>
-__global__ void __launch_bounds__(512) k_conv_rows(ConvArgs a) {
-    constexpr int C = 64, NWV = 8;
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint16_t *t_hi = reinterpret_cast<uint16_t *>(smem);                      // [2][64][64] bf16, chunk-swizzled (B operand of the R tiles)
-    uint16_t *t_lo = t_hi + 2 * TCELLS * C;
-    float *halo = reinterpret_cast<float *>(t_lo + 2 * TCELLS * C);           // [192][64] fp32
-    int32_t *idxh = reinterpret_cast<int32_t *>(halo + NSLOT * C);            // [2][256]
-    float *part = reinterpret_cast<float *>(idxh + 2 * 256);                  // [2][4][64]
-    float *w9s = part + 2 * 4 * TCELLS;                                       // [9][64]
-    float *b9s = w9s + 9 * C;
-    float *r0s = b9s + C;
-    uint16_t *r_hi = reinterpret_cast<uint16_t *>(r0s + C);                   // [64][64]
-    uint16_t *r_lo = r_hi + C * C;
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l15 = lane & 15, g4 = lane >> 4;
-    const int tw = a.W / TS;
-    const int n_live = a.counts[0];
-    const int64_t n_groups = ((int64_t)n_live + NPIECE - 1) / NPIECE;
-    const int64_t g_begin = blockIdx.x, g_end = n_groups, g_step = gridDim.x;
-
-    for (int e = tid; e < 9 * C; e += 512) w9s[e] = a.w9[(e % C) * 9 + e / C];
-    if (tid < C) { b9s[tid] = a.b9 ? a.b9[tid] : 0.f; r0s[tid] = a.r0[tid]; }
-    for (int e = tid; e < C * C / 8; e += 512) {
-        reinterpret_cast<u32x4 *>(r_hi)[e] = reinterpret_cast<const u32x4 *>(a.rh)[e];
-        if (X3) reinterpret_cast<u32x4 *>(r_lo)[e] = reinterpret_cast<const u32x4 *>(a.rl)[e];
-    }
-    auto load_idx = [&](int64_t g, int &code_out) -> int {
-        code_out = -1;
-        if (tid >= NSLOT) return -1;
-        const int j = tid / PHALO, hc = tid - j * PHALO;
-        const int64_t k = g * NPIECE + j;
-        if (k >= n_live) return -1;
-        const int code = a.live_list[k];
-        code_out = code;
-        const int p = code & 7, ts = code >> 3, t = ts / a.S, sc = ts - t * a.S;
-        int y0, x0;
-        piece_origin(t, p, tw, y0, x0);
-        const int gy = y0 - 1 + hc / PW, gx = x0 - 1 + hc % PW;
-        return (gy >= 0 && gy < a.H && gx >= 0 && gx < a.W) ? a.idx[((int64_t)sc * a.H + gy) * a.W + gx] : -1;
-    };
-    auto store_idx = [&](int32_t *ih, int v, int code) {
-        if (tid < NSLOT) {
-            ih[tid] = v;
-            if (tid % PHALO == 0) ih[200 + tid / PHALO] = code;
-        }
-    };
-    auto dma_halo = [&](const int32_t *ih) {
-        for (int q = wid; q < NSLOT / 4; q += NWV) {
-            const int slot = q * 4 + (lane >> 4);
-            const int row = ih[slot];
-            if (row >= 0)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(a.feat + (int64_t)row * C + 4 * l15),
-                                                 (__attribute__((address_space(3))) void *)(halo + q * 4 * C), 16, 0, 0);
-        }
-    };
-    // depthwise 3x3 + GELU (the tap order and fmaf chain of k_dwconv3x3_gelu); the dirty cells' tokens also leave for HBM right here
-    auto conv_tile = [&](const int32_t *ih, int buf, int64_t g) {
-        const int cell = tid >> 3, cg = (tid & 7) * 8, hb = (cell >> 3) * PHALO, cy = (cell >> 2) & 1, cx = cell & 3;
-        float acc[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) acc[c] = b9s[cg + c];
-#pragma unroll
-        for (int rr = 0; rr < 3; ++rr)
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const int slot = hb + (cy + rr) * PW + cx + k;
-                if (ih[slot] >= 0) {
-                    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(halo + slot * C + cg), v1 = *reinterpret_cast<const f32x4 *>(halo + slot * C + cg + 4);
-                    const f32x4 k0 = *reinterpret_cast<const f32x4 *>(w9s + (rr * 3 + k) * C + cg), k1 = *reinterpret_cast<const f32x4 *>(w9s + (rr * 3 + k) * C + cg + 4);
-#pragma unroll
-                    for (int c = 0; c < 4; ++c) { acc[c] = fmaf(v0[c], k0[c], acc[c]); acc[4 + c] = fmaf(v1[c], k1[c], acc[4 + c]); }
-                }
-            }
-        uint32_t hi[4], lo[4];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const float y0 = gelu_erf(acc[2 * c]), y1 = gelu_erf(acc[2 * c + 1]);
-            hi[c] = pack_bf16(y0, y1);
-            lo[c] = pack_bf16(y0 - __uint_as_float(hi[c] << 16), y1 - __uint_as_float(hi[c] & 0xffff0000u));
-        }
-        const int ch = (tid & 7) ^ ((cell >> 1) & 7);
-        *reinterpret_cast<u32x4 *>(t_hi + (buf * TCELLS + cell) * C + ch * 8) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-        if (X3) *reinterpret_cast<u32x4 *>(t_lo + (buf * TCELLS + cell) * C + ch * 8) = u32x4{lo[0], lo[1], lo[2], lo[3]};
-        const int code = ih[200 + (cell >> 3)];
-        if (code >= 0) {
-            const int2 pd = a.piece_dirty[g * NPIECE + (cell >> 3)];
-            if ((pd.y >> (cell & 7)) & 1) {
-                const int64_t orow = pd.x + __popc((unsigned)pd.y & ((1u << (cell & 7)) - 1u));
-                *reinterpret_cast<u32x4 *>(a.th + orow * C + cg) = u32x4{hi[0], hi[1], hi[2], hi[3]};
-                if (X3) *reinterpret_cast<u32x4 *>(a.tl + orow * C + cg) = u32x4{lo[0], lo[1], lo[2], lo[3]};
-            }
-        }
-    };
-    auto load_t = [&](int buf, int gq, bf16x8 &th0, bf16x8 &th1, bf16x8 &tl0, bf16x8 &tl1) {
-        const int row = gq * 16 + l15;
-        const int c0 = (g4 ^ ((row >> 1) & 7)) * 8, c1 = ((4 + g4) ^ ((row >> 1) & 7)) * 8;
-        th0 = *reinterpret_cast<const bf16x8 *>(t_hi + (buf * TCELLS + row) * C + c0);
-        th1 = *reinterpret_cast<const bf16x8 *>(t_hi + (buf * TCELLS + row) * C + c1);
-        if (X3) {
-            tl0 = *reinterpret_cast<const bf16x8 *>(t_lo + (buf * TCELLS + row) * C + c0);
-            tl1 = *reinterpret_cast<const bf16x8 *>(t_lo + (buf * TCELLS + row) * C + c1);
-        }
-    };
-
-    if (tid < 256) { idxh[tid] = -1; idxh[256 + tid] = -1; }
-    __syncthreads();
-    if (g_begin >= g_end) return;
-    {
-        int c0, c1;
-        const int i0 = load_idx(g_begin, c0);
-        const int i1 = g_begin + g_step < g_end ? load_idx(g_begin + g_step, c1) : (c1 = -1, -1);
-        store_idx(idxh, i0, c0);
-        store_idx(idxh + 256, i1, c1);
-    }
-    __syncthreads();
-    dma_halo(idxh);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    conv_tile(idxh, 0, g_begin);
-    int buf = 0;
-    for (int64_t g = g_begin, it = 0; g < g_end; g += g_step, ++it) {
-        __syncthreads();                                          // B1: t[buf] complete, halo buffer free, part[buf] free
-        const int32_t *ih_cur = idxh + (it & 1) * 256, *ih_nx = idxh + ((it + 1) & 1) * 256;
-        const bool has_nx = g + g_step < g_end, has_n2 = g + 2 * g_step < g_end;
-        if (has_nx) dma_halo(ih_nx);
-        const int my_code = tid < TCELLS ? ih_cur[200 + (tid >> 3)] : -1;     // piece code of cell tid (threads 0..63 finish the rows)
-        int c2 = -1;
-        const int i2 = has_n2 ? load_idx(g + 2 * g_step, c2) : -1;
-        // |R t + r0|^2 per cell: wave w takes the 16-row tile w & 3 of R for the 16-cell groups 2 (w >> 2), 2 (w >> 2) + 1
-        {
-            const int rt = wid & 3;
-            const uint16_t *rp = r_hi + (16 * rt + l15) * C + 8 * g4, *rpl = r_lo + (16 * rt + l15) * C + 8 * g4;
-            const bf16x8 ra0 = *reinterpret_cast<const bf16x8 *>(rp), ra1 = *reinterpret_cast<const bf16x8 *>(rp + 32);
-            bf16x8 rl0 = ra0, rl1 = ra1;
-            if (X3) { rl0 = *reinterpret_cast<const bf16x8 *>(rpl); rl1 = *reinterpret_cast<const bf16x8 *>(rpl + 32); }
-            const f32x4 rinit = *reinterpret_cast<const f32x4 *>(r0s + 16 * rt + 4 * g4);
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const int gq = 2 * (wid >> 2) + u;
-                bf16x8 th0, th1, tl0, tl1;
-                load_t(buf, gq, th0, th1, tl0, tl1);
-                f32x4 v = rinit;
-                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra0, th0, v, 0, 0, 0);
-                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra1, th1, v, 0, 0, 0);
-                if (X3) {
-                    v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra0, tl0, v, 0, 0, 0);
-                    v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra1, tl1, v, 0, 0, 0);
-                    v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl0, th0, v, 0, 0, 0);
-                    v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl1, th1, v, 0, 0, 0);
-                }
-                float sq = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
-                sq += __shfl_xor(sq, 16);
-                sq += __shfl_xor(sq, 32);
-                if (g4 == 0) part[(buf * 4 + rt) * TCELLS + gq * 16 + l15] = sq;
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // this wave's halo DMA (next group) has landed
-        __syncthreads();                                          // B2: partial sums complete; every wave's DMA landed; codes of this group read
-        store_idx(idxh + (it & 1) * 256, i2, c2);
-        if (tid < TCELLS && my_code >= 0) {                        // rstd and key of this group's dirty cells
-            const int cell = tid;
-            const int2 pd = a.piece_dirty[g * NPIECE + (cell >> 3)];
-            if ((pd.y >> (cell & 7)) & 1) {
-                const int64_t orow = pd.x + __popc((unsigned)pd.y & ((1u << (cell & 7)) - 1u));
-                const float *pr = part + buf * 4 * TCELLS;
-                const float ss = (pr[cell] + pr[TCELLS + cell]) + (pr[2 * TCELLS + cell] + pr[3 * TCELLS + cell]) + a.c0;
-                a.rstd[orow] = 1.0f / sqrtf(ss * a.inv_d + a.eps);
-                a.key[orow] = ((my_code >> 3) / a.S) * TCELLS + (my_code & 7) * PCELLS + (cell & 7);
-            }
-        }
-        if (has_nx) conv_tile(ih_nx, buf ^ 1, g + g_step);
-        buf ^= 1;
-    }
-}
-
-struct KvRowArgs {
-    const uint16_t *th, *tl;      // t rows [n, 64] bf16 hi / lo
-    const float *rstd;            // [n]
-    const int32_t *key;           // [n]
-    const int32_t *n_rows;        // device-side row count
-    const uint16_t *mh, *ml;      // M [2 N, 64] bf16 hi / lo
-    const float *m0;              // [2 N]
-    const float *te;              // T [keys, 2 N] fp32
-    uint16_t *out;                // K|V rows [n, 2 N] bf16 (the K half as IEEE fp16 when k_fp16)
-    int k_fp16;
-};
-
-// The loads of k_kv_rows' tile loop as inline asm.  The compiler's wait pass does not count them, and that is the point: with an LDS-DMA
+// The loop's vector-memory loads as inline asm.  The compiler's wait pass does not count them, and that is the point: with an LDS-DMA
 // outstanding it waits vmcnt(0) at the first use of any load it does count and at every __syncthreads(), which put eight full drains
-// into a tile and made the "one group ahead" T request wait for itself.  Every load of the loop is therefore issued here, every wait is
-// a vm_wait<N>() counted by hand in the kernel, and a destination register is handed to the compiler (landed()) only behind the wait
+// into a tile of k_kv_rows and a drain per barrier into k_conv_rows.  Every load of such a loop is therefore issued here, every wait is
+// a vm_wait<N>() placed by hand in the kernel, and a destination register is handed to the compiler (landed()) only behind the wait
 // that retires it.  Vector-memory operations complete in issue order, so vmcnt(N) retires everything but the newest N.
+typedef int i32x2 __attribute__((ext_vector_type(2)));
 template <int N> __device__ __forceinline__ void vm_wait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 template <int OFF> __device__ __forceinline__ void vm_load16(f32x4 &d, const void *p) {       // early clobber: d never overlaps the address pair
     asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=&v"(d) : "v"(p), "n"(OFF) : "memory");
 }
+__device__ __forceinline__ void vm_load8(i32x2 &d, const void *p) { asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(d) : "v"(p) : "memory"); }
 template <class T> __device__ __forceinline__ void vm_load4(T &d, const void *p) {
     static_assert(sizeof(T) == 4, "one dword");
     asm volatile("global_load_dword %0, %1, off" : "=&v"(d) : "v"(p) : "memory");
@@ -1156,6 +971,254 @@ __device__ __forceinline__ void vm_dma16(const void *src, uint32_t dst) {
 template <class T> __device__ __forceinline__ void landed(T &x) { asm volatile("" : "+v"(x)); }
 template <int... I, class F> __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F &&f) { (f(std::integral_constant<int, I>{}), ...); }
 template <int N, class F> __device__ __forceinline__ void static_for(F &&f) { static_for(std::make_integer_sequence<int, N>{}, f); }
+// workgroup barrier without the memory drain of __syncthreads(): LDS traffic of this wave complete, vector memory left in flight
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+// A workgroup walks its groups (ordinal o = 0, 1, ... : group blockIdx.x + o gridDim.x) as a five-deep software pipeline.  One pass of
+// the loop (`it`) holds, in issue order:
+//     halo DMA of ordinal it + 2          (its index words reached LDS a pass ago; the second halo buffer lets it fly for a whole pass)
+//     index words of ordinal it + 3       (one dword per halo slot; the piece codes they depend on are in the LDS ring since a pass ago)
+//     codes + dirty entries of it + 4     (8 ints + 8 int2, fetched once per group into the ring -- not per thread before each use)
+//     rstd / key stores of ordinal it     (wave 7; sums from `part`, row numbers from the ring)
+//     conv of ordinal it + 1, t stores    (halo landed and index words visible since the barrier that ended the previous pass)
+//     barrier B1                          (t complete)
+//     |R t + r0|^2 of ordinal it + 1      (R fragments are loop-invariant per wave: registers, not LDS)
+//     vm_wait<0>                          (the pass's ONE wait: DMA, index words and ring entries have had the conv and the MFMA batch to
+//                                          land, so what it exposes is the tail of one round trip, not three or four in a row; it also
+//                                          retires the pass's stores, the youngest of which are a MFMA batch old)
+//     index words / ring entries -> LDS, barrier B2
+// Nothing the loop loads is counted by the compiler (inline asm), the barriers are raw, and its stores are never waited for by the
+// compiler, so the one wait is the only drain.  Every asm load is issued and retired inside one pass and by every thread (clamped
+// address, result discarded where it does not apply): no destination register is live across the back edge or merged under a branch.
+template <bool X3>
+__global__ void __launch_bounds__(512) k_conv_rows(ConvArgs a) {
+    constexpr int C = 64, NWV = 8, RING = 8;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    uint16_t *t_hi = reinterpret_cast<uint16_t *>(smem);                      // [64][64] bf16, chunk-swizzled (B operand of the R tiles)
+    uint16_t *t_lo = t_hi + TCELLS * C;
+    float *halo = reinterpret_cast<float *>(t_lo + TCELLS * C);               // [2][192][64] fp32
+    int32_t *idxh = reinterpret_cast<int32_t *>(halo + 2 * NSLOT * C);        // [2][256] halo index words of two ordinals
+    int32_t *mcode = idxh + 2 * 256;                                          // [RING][8] piece codes (-1: no piece)
+    i32x2 *mdirty = reinterpret_cast<i32x2 *>(mcode + RING * NPIECE);         // [RING][8] (first dirty-row number, dirty mask)
+    float *part = reinterpret_cast<float *>(mdirty + RING * NPIECE);          // [4][64]
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6, l15 = lane & 15, g4 = lane >> 4;
+    const int tw = a.W / TS;
+    const int n_live = a.counts[0];
+    const int64_t n_groups = ((int64_t)n_live + NPIECE - 1) / NPIECE;
+    const int64_t g_begin = blockIdx.x, g_step = gridDim.x;
+    if (g_begin >= n_groups) return;
+    const int n_my = (int)((n_groups - g_begin + g_step - 1) / g_step);       // ordinals 0 .. n_my - 1 exist; later ones are empty
+
+    // conv weights and bias: a thread convolves the same 8 channels (tid & 7) in every group -- 72 + 8 registers instead of 288 B of LDS
+    // reads per thread and group (half of the conv's LDS traffic was weights)
+    float wk[9][8], bk[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const int ch = (tid & 7) * 8 + c;
+        bk[c] = a.b9 ? a.b9[ch] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) wk[k][c] = a.w9[ch * 9 + k];
+    }
+    // R: wave w multiplies the 16-row tile w & 3 in every group -- its four fragments and its slice of r0 stay in registers
+    const int rt = wid & 3;
+    bf16x8 ra0, ra1, rl0, rl1;
+    {
+        const uint16_t *rp = a.rh + (16 * rt + l15) * C + 8 * g4;
+        ra0 = *reinterpret_cast<const bf16x8 *>(rp);
+        ra1 = *reinterpret_cast<const bf16x8 *>(rp + 32);
+        rl0 = ra0; rl1 = ra1;
+        if (X3) {
+            const uint16_t *rpl = a.rl + (16 * rt + l15) * C + 8 * g4;
+            rl0 = *reinterpret_cast<const bf16x8 *>(rpl);
+            rl1 = *reinterpret_cast<const bf16x8 *>(rpl + 32);
+        }
+    }
+    f32x4 rinit = *reinterpret_cast<const f32x4 *>(a.r0 + 16 * rt + 4 * g4);
+
+    // ring entry of piece j of ordinal o: is there such a piece, and where
+    auto piece_k = [&](int o, int j, bool &ok) -> int64_t {
+        const int64_t grp = g_begin + (int64_t)o * g_step, k = grp * NPIECE + j;
+        ok = o < n_my && k < n_live;
+        return ok ? k : 0;
+    };
+    // this thread's halo slot of ordinal o (its codes are in the ring): offset of its index word in a.idx; !ok: no such slot, or outside the BEV
+    auto idx_off = [&](int o, bool &ok) -> int64_t {
+        ok = false;
+        if (tid >= NSLOT) return 0;
+        const int j = tid / PHALO, hc = tid - j * PHALO;
+        const int code = mcode[(o & (RING - 1)) * NPIECE + j];
+        if (code < 0) return 0;
+        const int p = code & 7, ts = code >> 3, t = ts / a.S, sc = ts - t * a.S;
+        int y0, x0;
+        piece_origin(t, p, tw, y0, x0);
+        const int gy = y0 - 1 + hc / PW, gx = x0 - 1 + hc % PW;
+        if (gy < 0 || gy >= a.H || gx < 0 || gx >= a.W) return 0;
+        ok = true;
+        return ((int64_t)sc * a.H + gy) * a.W + gx;
+    };
+    const uint32_t lds_halo = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) float *)halo);
+    auto dma_halo = [&](const int32_t *ih, int hbuf) {
+        for (int q = wid; q < NSLOT / 4; q += NWV) {
+            const int row = ih[q * 4 + (lane >> 4)];
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(lds_halo + (uint32_t)((hbuf * NSLOT + q * 4) * C * 4));
+            if (row >= 0) vm_dma16(a.feat + (int64_t)row * C + 4 * l15, dst);
+        }
+    };
+    // depthwise 3x3 + GELU (the tap order and fmaf chain of k_dwconv3x3_gelu); the dirty cells' tokens also leave for HBM right here
+    auto conv_tile = [&](const int32_t *ih, const float *hl, int o) {
+        const int cell = tid >> 3, cg = (tid & 7) * 8, hb = (cell >> 3) * PHALO, cy = (cell >> 2) & 1, cx = cell & 3;
+        float acc[8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c) acc[c] = bk[c];
+#pragma unroll
+        for (int rr = 0; rr < 3; ++rr)
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int slot = hb + (cy + rr) * PW + cx + k;
+                if (ih[slot] >= 0) {
+                    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(hl + slot * C + cg), v1 = *reinterpret_cast<const f32x4 *>(hl + slot * C + cg + 4);
+                    const float *kk = wk[rr * 3 + k];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) { acc[c] = fmaf(v0[c], kk[c], acc[c]); acc[4 + c] = fmaf(v1[c], kk[4 + c], acc[4 + c]); }
+                }
+            }
+        uint32_t hi[4], lo[4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const float y0 = gelu_erf(acc[2 * c]), y1 = gelu_erf(acc[2 * c + 1]);
+            hi[c] = pack_bf16(y0, y1);
+            lo[c] = pack_bf16(y0 - __uint_as_float(hi[c] << 16), y1 - __uint_as_float(hi[c] & 0xffff0000u));
+        }
+        const int ch = (tid & 7) ^ ((cell >> 1) & 7);
+        *reinterpret_cast<u32x4 *>(t_hi + cell * C + ch * 8) = u32x4{hi[0], hi[1], hi[2], hi[3]};
+        if (X3) *reinterpret_cast<u32x4 *>(t_lo + cell * C + ch * 8) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+        const int m = (o & (RING - 1)) * NPIECE + (cell >> 3);
+        if (mcode[m] >= 0) {
+            const i32x2 pd = mdirty[m];
+            if ((pd.y >> (cell & 7)) & 1) {
+                const int64_t orow = pd.x + __popc((unsigned)pd.y & ((1u << (cell & 7)) - 1u));
+                *reinterpret_cast<u32x4 *>(a.th + orow * C + cg) = u32x4{hi[0], hi[1], hi[2], hi[3]};
+                if (X3) *reinterpret_cast<u32x4 *>(a.tl + orow * C + cg) = u32x4{lo[0], lo[1], lo[2], lo[3]};
+            }
+        }
+    };
+    // |R t + r0|^2 per cell: wave w takes the 16-row tile w & 3 of R for the 16-cell groups 2 (w >> 2), 2 (w >> 2) + 1
+    auto row_sums = [&]() {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int gq = 2 * (wid >> 2) + u;
+            const int row = gq * 16 + l15;
+            const int c0 = (g4 ^ ((row >> 1) & 7)) * 8, c1 = ((4 + g4) ^ ((row >> 1) & 7)) * 8;
+            const bf16x8 th0 = *reinterpret_cast<const bf16x8 *>(t_hi + row * C + c0), th1 = *reinterpret_cast<const bf16x8 *>(t_hi + row * C + c1);
+            f32x4 v = rinit;
+            v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra0, th0, v, 0, 0, 0);
+            v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra1, th1, v, 0, 0, 0);
+            if (X3) {
+                const bf16x8 tl0 = *reinterpret_cast<const bf16x8 *>(t_lo + row * C + c0), tl1 = *reinterpret_cast<const bf16x8 *>(t_lo + row * C + c1);
+                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra0, tl0, v, 0, 0, 0);
+                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ra1, tl1, v, 0, 0, 0);
+                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl0, th0, v, 0, 0, 0);
+                v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl1, th1, v, 0, 0, 0);
+            }
+            float sq = (v[0] * v[0] + v[1] * v[1]) + (v[2] * v[2] + v[3] * v[3]);
+            sq += __shfl_xor(sq, 16);
+            sq += __shfl_xor(sq, 32);
+            if (g4 == 0) part[rt * TCELLS + gq * 16 + l15] = sq;
+        }
+    };
+    // rstd and key of ordinal o's dirty cells: the last wave, one cell per lane (waves 0..2 already carry the index-word addresses)
+    auto finish_rows = [&](int o) {
+        if (wid != NWV - 1) return;
+        const int cell = lane, m = (o & (RING - 1)) * NPIECE + (cell >> 3);
+        const int code = mcode[m];
+        if (code < 0) return;
+        const i32x2 pd = mdirty[m];
+        if ((pd.y >> (cell & 7)) & 1) {
+            const int64_t orow = pd.x + __popc((unsigned)pd.y & ((1u << (cell & 7)) - 1u));
+            const float ss = (part[cell] + part[TCELLS + cell]) + (part[2 * TCELLS + cell] + part[3 * TCELLS + cell]) + a.c0;
+            a.rstd[orow] = 1.0f / sqrtf(ss * a.inv_d + a.eps);
+            a.key[orow] = ((code >> 3) / a.S) * TCELLS + (code & 7) * PCELLS + (cell & 7);
+        }
+    };
+
+    // ---- prologue (once per workgroup, plain loads and full barriers): ring entries of ordinals 0..3, index words of 0..2, halos of 0 and 1,
+    // conv and row sums of ordinal 0
+    if (tid < 4 * NPIECE) {
+        bool ok;
+        const int64_t k = piece_k(tid >> 3, tid & 7, ok);
+        const int code = a.live_list[k];
+        const int2 pd = a.piece_dirty[k];
+        mcode[tid] = ok ? code : -1;
+        mdirty[tid] = ok ? i32x2{pd.x, pd.y} : i32x2{0, 0};
+    }
+    __syncthreads();
+    {
+        bool k0, k1, k2;
+        const int64_t o0 = idx_off(0, k0), o1 = idx_off(1, k1), o2 = idx_off(2, k2);
+        const int i0 = a.idx[o0], i1 = a.idx[o1], i2 = a.idx[o2];
+        if (tid < 256) { idxh[tid] = k0 ? i0 : -1; idxh[256 + tid] = k1 ? i1 : -1; }
+        __syncthreads();
+        dma_halo(idxh, 0);
+        dma_halo(idxh + 256, 1);
+        vm_wait<0>();                                             // both halos; the R fragments and conv weights (the compiler's own loads end here)
+        landed(ra0); landed(ra1); landed(rl0); landed(rl1); landed(rinit);
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            landed(bk[c]);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) landed(wk[k][c]);
+        }
+        __syncthreads();
+        conv_tile(idxh, halo, 0);
+        __syncthreads();
+        row_sums();
+        if (tid < 256) idxh[tid] = k2 ? i2 : -1;                  // ordinal 2 takes over ordinal 0's words
+        __syncthreads();
+    }
+    for (int it = 0; it < n_my; ++it) {
+        // here: `part` holds ordinal it; halo[(it + 1) & 1] holds ordinal it + 1; index words of it + 1, it + 2 and ring entries up to it + 3 are in LDS
+        const int cur = it & 1, nx = cur ^ 1;
+        const bool has_nx = it + 1 < n_my;
+        dma_halo(idxh + cur * 256, cur);                          // ordinal it + 2 into the buffer that the conv of ordinal it left before B2
+        bool ok_i, ok_m;
+        const int64_t off_i = idx_off(it + 3, ok_i);
+        const int64_t k_m = piece_k(it + 4, tid & 7, ok_m);
+        int iw, mc;
+        i32x2 md;
+        vm_load4(iw, a.idx + off_i);
+        vm_load4(mc, a.live_list + k_m);
+        vm_load8(md, a.piece_dirty + k_m);
+        finish_rows(it);
+        if (has_nx) conv_tile(idxh + nx * 256, halo + nx * NSLOT * C, it + 1);
+        lds_barrier();                                            // B1: t complete; `part` read
+        if (has_nx) row_sums();
+        vm_wait<0>();                                             // retires this pass's DMA, index words, ring entries and stores
+        landed(iw); landed(mc); landed(md);
+        if (tid < 256) idxh[nx * 256 + tid] = ok_i ? iw : -1;     // ordinal it + 3 takes over ordinal it + 1's words (its conv is behind B1)
+        if (tid < NPIECE) {
+            const int m = ((it + 4) & (RING - 1)) * NPIECE + tid;
+            mcode[m] = ok_m ? mc : -1;
+            mdirty[m] = ok_m ? md : i32x2{0, 0};
+        }
+        lds_barrier();                                            // B2: `part`, every wave's DMA, the index words and the ring entries are visible
+    }
+}
+
+struct KvRowArgs {
+    const uint16_t *th, *tl;      // t rows [n, 64] bf16 hi / lo
+    const float *rstd;            // [n]
+    const int32_t *key;           // [n]
+    const int32_t *n_rows;        // device-side row count
+    const uint16_t *mh, *ml;      // M [2 N, 64] bf16 hi / lo
+    const float *m0;              // [2 N]
+    const float *te;              // T [keys, 2 N] fp32
+    uint16_t *out;                // K|V rows [n, 2 N] bf16 (the K half as IEEE fp16 when k_fp16)
+    int k_fp16;
+};
 
 // TH: the table T is IEEE fp16 (its values are bounded by the fold; the rounding, 2^-12, disappears under the bf16 rounding of the result):
 // half the L2 traffic of the kernel's largest stream.  A lane then owns 8 consecutive columns per PAIR of column tiles, so one 16-byte
@@ -1500,12 +1563,15 @@ extern "C" int lvq_bev_tile_kv(const float *pillar_feat, const int32_t *idx_map,
         c.feat = pillar_feat; c.idx = idx_map; c.live_list = live_list; c.piece_dirty = a.piece_dirty; c.counts = counts; c.w9 = w9; c.b9 = b9;
         c.rh = r; c.rl = r_lo; c.r0 = r0; c.c0 = c0; c.inv_d = a.inv_d; c.eps = eps; c.S = batch; c.H = ny; c.W = nx;
         c.th = th; c.tl = x3 ? tl : nullptr; c.rstd = rstd; c.key = key;
-        const size_t lds = (size_t)2 * 2 * bt::TCELLS * 64 * 2 + (size_t)bt::NSLOT * 64 * 4 + 2 * 256 * 4 + (size_t)2 * 4 * bt::TCELLS * 4 + 9 * 64 * 4 +
-                           64 * 4 + 64 * 4 + (size_t)2 * 64 * 64 * 2;
+        // t hi + lo, two fp32 halos, index words of two groups, the 8-deep ring of piece codes and dirty entries, row-sum partials
+        const size_t lds = (size_t)2 * bt::TCELLS * 64 * 2 + (size_t)2 * bt::NSLOT * 64 * 4 + 2 * 256 * 4 + (size_t)8 * bt::NPIECE * (4 + 8) +
+                           (size_t)4 * bt::TCELLS * 4;
         static LvqLdsOnce once;
         if (!lvq_ensure_lds(once, {(const void *)bt::k_conv_rows<false>, (const void *)bt::k_conv_rows<true>}, lds)) return LVQ_ELAUNCH;
         int64_t grid = (int64_t)lvq_cu_count();
-        if (grid > cap_tiles) grid = cap_tiles;
+        const int hook = lvq_tune().conv_rows_grid;                // test hook: small inputs give a workgroup 0, 1, 2, 3 ... groups
+        if (hook > 0) grid = hook < grid ? hook : grid;
+        else if (grid > cap_tiles) grid = cap_tiles;
         if (x3) hipLaunchKernelGGL((bt::k_conv_rows<true>), dim3((unsigned)grid), dim3(512), lds, st, c);
         else    hipLaunchKernelGGL((bt::k_conv_rows<false>), dim3((unsigned)grid), dim3(512), lds, st, c);
         bt::KvRowArgs k;
