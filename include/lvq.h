@@ -378,6 +378,27 @@ int lvq_attention_bf16(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *
                        int64_t v_hstride, int64_t o_bstride, int64_t ldo, int64_t o_hstride, float scale, int causal,
                        lvq_bf16 *o, lvq_bf16 *o_lo, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
+/* ---- Grid self-attention with the decomposed relative-position bias (csrc/vit_attention.hip) ---------------------------------
+ * The attention of the SAM / ViTDet image encoder (deepencoder/sam_vary_sdpa.py:269-296 with add_decomposed_rel_pos 382-413 and
+ * get_rel_pos 348-379 at q_size == k_size), for a windowed block (grid = one window) and a global block (grid = the image) alike:
+ *   O[b, i, h, :] = softmax_j( scale q_i.k_j + q_i.Rh[y_i - y_j + gh - 1] + q_i.Rw[x_i - x_j + gw - 1] ) v_j
+ *   i = y_i gw + x_i, j = y_j gw + x_j over the gh x gw grid of batch entry b; the bias terms use the UNSCALED q; statistics and
+ *   accumulation in fp32.  The bias is formed inside the kernel from the two tables: no array of size (gh gw)^2 is read or written.
+ *   qkv     the packed projection as Attention.qkv emits it: [batch * gh * gw, 3 * n_heads * dh] rows ld_qkv apart (elements),
+ *           column = part * n_heads * dh + h * dh + e, part 0 / 1 / 2 = q / k / v
+ *   rel_h   [2 gh - 1, dh], rel_w [2 gw - 1, dh], dense rows (tables of another length are resized by the caller, once per weights)
+ *   o       [batch * gh * gw, n_heads * dh] rows ldo apart: the A operand of the output projection; o_lo (optional) = fp32 result - o
+ *   forms   qkv_lo, rel_h_lo, rel_w_lo all NULL: plain bf16; all non-NULL: bf16x3 (scores, bias products and P V as hi + lo)
+ * Family: dh == 64, 1 <= gh, gw <= 64, any batch and head count; otherwise LVQ_EUNSUPPORTED (lvq_attention_relpos_ok is that rule).
+ * ld_qkv a multiple of 8, ldo of 4, 16-byte aligned operands, 8-byte aligned outputs (else LVQ_EUNSUPPORTED); ws_bytes below
+ * lvq_attention_relpos_workspace_bytes: LVQ_EWORKSPACE.  Every refusal happens before any launch, outputs untouched. */
+int lvq_attention_relpos_ok(int gh, int gw, int dh);
+size_t lvq_attention_relpos_workspace_bytes(int batch, int n_heads, int gh, int gw, int dh, int precision);
+int lvq_attention_relpos_bf16(const lvq_bf16 *qkv, const lvq_bf16 *qkv_lo, int64_t ld_qkv, const lvq_bf16 *rel_h,
+                              const lvq_bf16 *rel_h_lo, const lvq_bf16 *rel_w, const lvq_bf16 *rel_w_lo, int batch, int n_heads,
+                              int gh, int gw, int dh, float scale, lvq_bf16 *o, lvq_bf16 *o_lo, int64_t ldo, void *ws,
+                              size_t ws_bytes, lvq_stream_t stream);
+
 /* ---- Fused short-K/V cross-attention sub-path (csrc/cross_fused.hip) -------------------------------------------------------
  * out = q + ca(ca_ln(q), kv, kv): encoder-decoder/training/models/vat_blocks.py:41-42 (nn.LayerNorm + nn.MultiheadAttention with
  * batch_first, eval mode) as TWO launches: the K|V projection of the kv tokens (written straight in MFMA fragment order into `ws`)

@@ -5,6 +5,7 @@ directory, whose on-disk name carries a hyphen).  Sub-packages:
 
   lidar   voxeliser / VFE / BEV-scatter plugins with the OpenPCDet `batch_dict` protocol
   fusion  VATBlock / VATLiDAR / VATVision / VisionAdapter with the reference's nn.Module API
+  vision_tower  the SAM ViT image encoder (ImageEncoderViT, build_sam_vit_b) with the reference's nn.Module API
   head    prefix assembly + stand-in decoder head
   dist    scene sharding + fused all-reduce over RCCL
   _ffi    ctypes binding of the C-ABI library built from csrc/ (include/lvq.h)

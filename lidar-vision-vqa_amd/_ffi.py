@@ -138,7 +138,8 @@ def lib() -> ctypes.CDLL:
                      "lvq_attention_stream_totals_workspace_bytes", "lvq_attention_tiled_signed_workspace_bytes",
                      "lvq_bev_tile_kv_workspace_bytes", "lvq_ca_fused_packed_bytes", "lvq_ca_fused_workspace_bytes",
                      "lvq_attention_decode_ragged_workspace_bytes", "lvq_qwen2_decode_ragged_workspace_bytes",
-                     "lvq_attention_extend_shared_workspace_bytes", "lvq_qwen2_extend_shared_workspace_bytes"):
+                     "lvq_attention_extend_shared_workspace_bytes", "lvq_qwen2_extend_shared_workspace_bytes",
+                     "lvq_attention_relpos_workspace_bytes"):
             getattr(L, name).restype = ctypes.c_size_t
         L.lvq_tuning_defaults.restype = None
         _lib = L

@@ -173,6 +173,35 @@ def attention(q: BF, k: BF, v: BF, *, batch: int, n_heads: int, n_kv_heads: int,
     return oh, ol
 
 
+def attention_relpos_ok(gh: int, gw: int, dh: int) -> bool:
+    """lvq_attention_relpos_ok: the fused grid attention with decomposed relative-position bias takes (gh, gw, dh)."""
+    return bool(F.lib().lvq_attention_relpos_ok(F.cint(gh), F.cint(gw), F.cint(dh)))
+
+
+def attention_relpos(qkv: BF, rel_h: BF, rel_w: BF, *, batch: int, n_heads: int, gh: int, gw: int, dh: int, scale: float,
+                     tag: Optional[str] = None) -> BF:
+    """lvq_attention_relpos_bf16.  qkv: BF [batch * gh * gw, >= 3 * n_heads * dh] (the packed projection, row stride = its width);
+    rel_h [2 gh - 1, dh], rel_w [2 gw - 1, dh].  Returns BF [batch * gh * gw, n_heads * dh]."""
+    qh, ql = qkv
+    dev = qh.device
+    split = ql is not None
+    F.require_cuda(qh, ql, rel_h[0], rel_h[1], rel_w[0], rel_w[1])
+    if qh.dim() != 2 or qh.shape[0] != batch * gh * gw or tuple(rel_h[0].shape) != (2 * gh - 1, dh) or tuple(rel_w[0].shape) != (2 * gw - 1, dh):
+        raise F.LvqError(f"attention_relpos: qkv {tuple(qh.shape)}, rel_h {tuple(rel_h[0].shape)}, rel_w {tuple(rel_w[0].shape)} do not "
+                         f"fit batch {batch}, grid {gh} x {gw}, head dim {dh}")
+    oh, ol = _bf_empty((batch * gh * gw, n_heads * dh), dev, split)
+    L = F.lib()
+    nbytes = L.lvq_attention_relpos_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(gh), F.cint(gw), F.cint(dh), F.cint(3 if split else 1))
+    ws = _att_ws(dev, int(nbytes)) if nbytes else None
+    with region(tag, dev):
+        rc = L.lvq_attention_relpos_bf16(F.ptr(qh), F.ptr(ql), F.i64(qh.shape[1]), F.ptr(rel_h[0]), F.ptr(rel_h[1]), F.ptr(rel_w[0]),
+                                         F.ptr(rel_w[1]), F.cint(batch), F.cint(n_heads), F.cint(gh), F.cint(gw), F.cint(dh), F.cfloat(scale),
+                                         F.ptr(oh), F.ptr(ol), F.i64(n_heads * dh), F.ptr(ws), F.csize(ws.numel() if ws is not None else 0),
+                                         F.stream_ptr(dev))
+    F.check(rc, f"lvq_attention_relpos_bf16 (B={batch}, H={n_heads}, grid {gh} x {gw}, dh={dh})")
+    return oh, ol
+
+
 def attention_decode_ragged(q: BF, k_cache: BF, v_cache: BF, kv_len: torch.Tensor, *, batch: int, n_heads: int, n_kv_heads: int, lmax: int,
                             dh: int, q_strides, k_strides, v_strides, scale: float) -> BF:
     """One query token per sequence over the first kv_len[b] rows of its K / V cache (include/lvq.h: lvq_attention_decode_ragged).
