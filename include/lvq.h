@@ -391,8 +391,11 @@ int lvq_attention_bf16(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *
  *   forms   qkv_lo, rel_h_lo, rel_w_lo all NULL: plain bf16; all non-NULL: bf16x3 (scores, bias products and P V as hi + lo)
  * Family: dh == 64, 1 <= gh, gw <= 64, any batch and head count; otherwise LVQ_EUNSUPPORTED (lvq_attention_relpos_ok is that rule).
  * ld_qkv a multiple of 8, ldo of 4, 16-byte aligned operands, 8-byte aligned outputs (else LVQ_EUNSUPPORTED); ws_bytes below
- * lvq_attention_relpos_workspace_bytes: LVQ_EWORKSPACE.  Every refusal happens before any launch, outputs untouched. */
+ * lvq_attention_relpos_workspace_bytes: LVQ_EWORKSPACE.  Every refusal happens before any launch, outputs untouched.
+ * lvq_attention_relpos_plan (host only, a hook for tests): what a call on a gh x gw grid launches -- *stages = K | V stages in LDS (1 or 2),
+ * *lds_bytes = its dynamic LDS request; precision 1 (plain) or 3 (hi + lo), else LVQ_EINVAL; a grid outside the family LVQ_EUNSUPPORTED. */
 int lvq_attention_relpos_ok(int gh, int gw, int dh);
+int lvq_attention_relpos_plan(int gh, int gw, int precision, int *stages, size_t *lds_bytes);
 size_t lvq_attention_relpos_workspace_bytes(int batch, int n_heads, int gh, int gw, int dh, int precision);
 int lvq_attention_relpos_bf16(const lvq_bf16 *qkv, const lvq_bf16 *qkv_lo, int64_t ld_qkv, const lvq_bf16 *rel_h,
                               const lvq_bf16 *rel_h_lo, const lvq_bf16 *rel_w, const lvq_bf16 *rel_w_lo, int batch, int n_heads,

@@ -172,6 +172,15 @@ def require_cuda(*tensors: torch.Tensor):
             raise LvqError("tensor must be contiguous")
 
 
+def attention_relpos_plan(gh: int, gw: int, precision: int):
+    """lvq_attention_relpos_plan (host only, a hook for tests): (K | V stages, dynamic LDS bytes) of the kernel that the fused
+    relative-position attention launches on a gh x gw grid; precision 1 = plain bf16, 3 = hi + lo."""
+    stages, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
+    check(lib().lvq_attention_relpos_plan(cint(gh), cint(gw), cint(precision), ctypes.byref(stages), ctypes.byref(nbytes)),
+          f"lvq_attention_relpos_plan ({gh} x {gw}, precision {precision})")
+    return stages.value, nbytes.value
+
+
 def f32x(vals: Sequence[float]):
     return (ctypes.c_float * len(vals))(*[float(v) for v in vals])
 

@@ -351,6 +351,16 @@ LvqLdsOnce g_lds_relpos;
 
 extern "C" int lvq_attention_relpos_ok(int gh, int gw, int dh) { return dh == DH && gh >= 1 && gh <= 64 && gw >= 1 && gw <= 64; }
 
+// what lvq_attention_relpos_bf16 launches for a grid (host only): K | V stages and dynamic LDS bytes, from the functions the launch uses
+extern "C" int lvq_attention_relpos_plan(int gh, int gw, int precision, int *stages, size_t *lds_bytes) {
+    if ((precision != 1 && precision != 3) || !stages || !lds_bytes) return LVQ_EINVAL;
+    if (!lvq_attention_relpos_ok(gh, gw, DH)) return LVQ_EUNSUPPORTED;
+    const bool split = precision == 3;
+    *stages = rel_stages(gh, gw, split);
+    *lds_bytes = rel_lds_bytes(gh, gw, split, *stages);
+    return LVQ_OK;
+}
+
 // the fused kernel keeps its bias table in LDS: no workspace (the argument pair stays in the call for the family's convention)
 extern "C" size_t lvq_attention_relpos_workspace_bytes(int batch, int n_heads, int gh, int gw, int dh, int precision) {
     (void)batch; (void)n_heads; (void)gh; (void)gw; (void)dh; (void)precision;

@@ -5,7 +5,7 @@ Regime and bounds are those of tests/test_gpu_sparse_conv.py (whose sums, 27 x 1
 features, weights scaled by 1 / sqrt(taps C_in);  hi + lo operands 2e-4 max(1, max|ref|);  plain bf16 with operands rounded to bf16 on the
 host first (the reference sees the rounded values, so what is left is the fp32 accumulation) 2e-5 max(1, max|ref|).
 
-Every run writes BOTH output forms into a concat buffer 64 channels wider than the layer (channel offset 32) with a pre-filled tail: the
+Every run (but those that ask for one form, as the image encoder does) writes BOTH output forms into a concat buffer 64 channels wider than the layer (channel offset 32) with a pre-filled tail: the
 fp32 [B, C, H, W] result is held to the bound, the operand planes must be the bf16 hi / lo split of exactly those fp32 values, and
 everything outside the layer's channel and pixel range must keep the fill bit for bit.  The tile is 8 x 8 output pixels."""
 import numpy as np
@@ -49,8 +49,16 @@ def out_hw(kind, k, s, h, w):
     return ((h - 1) // s + 1, (w - 1) // s + 1) if k == 3 else (h // s, w // s)
 
 
-def run_layer(kind, x, wt, k, s, mode, scale=None, shift=None, relu=False, pad_c=64, c_off=32):
-    """-> fp32 [B, C_out, OH, OW] of the layer's own channel range, after the stray-write and plane checks."""
+def run_layer(kind, x, wt, k, s, mode, scale=None, shift=None, relu=False, pad_c=64, c_off=32, outputs="both"):
+    """-> fp32 [B, C_out, OH, OW] of the layer's own channel range, after the stray-write and plane checks (see run_forms)."""
+    return run_forms(kind, x, wt, k, s, mode, scale, shift, relu, pad_c, c_off, outputs)["f32"].cpu().numpy()
+
+
+def run_forms(kind, x, wt, k, s, mode, scale=None, shift=None, relu=False, pad_c=64, c_off=32, outputs="both"):
+    """One call that asks for `outputs`: "both" forms, the operand "planes" only (out_f32 == NULL) or "f32" only (out_hi == out_lo == NULL).
+    The buffers of a form that is not requested exist all the same and must keep their fill.  -> {"f32": [B, C_out, OH, OW] | None,
+    "hi", "lo": int16 [B, OH, OW, C_out] | None}: device tensors of the layer's own channel range, after the stray-write checks."""
+    assert outputs in ("both", "planes", "f32")
     L = B2._lib()
     d = torch.device(DEV)
     split = mode == "bf16x3"
@@ -72,7 +80,9 @@ def run_layer(kind, x, wt, k, s, mode, scale=None, shift=None, relu=False, pad_c
     p_lo = torch.full((n + TAIL,), FILL16, dtype=torch.int16, device=d) if split else None
     d_scale, d_shift = dev(scale), dev(shift)
     head = (F.ptr(xp.hi), F.ptr(xp.lo), F.cint(b), F.cint(h), F.cint(w), F.cint(cin), F.ptr(w_hi), F.ptr(w_lo), F.cint(cout))
-    tail = (F.ptr(d_scale), F.ptr(d_shift), F.cint(int(relu)), F.ptr(p_hi), F.ptr(p_lo), F.ptr(f32), F.cint(ct), F.cint(c_off), F.stream_ptr(d))
+    want_planes, want_f32 = outputs != "f32", outputs != "planes"
+    tail = (F.ptr(d_scale), F.ptr(d_shift), F.cint(int(relu)), F.ptr(p_hi if want_planes else None), F.ptr(p_lo if want_planes else None),
+            F.ptr(f32 if want_f32 else None), F.cint(ct), F.cint(c_off), F.stream_ptr(d))
     if kind == "deconv":
         rc = L.lvq_deconv2d(*head, F.cint(s), *tail)
     else:
@@ -84,15 +94,25 @@ def run_layer(kind, x, wt, k, s, mode, scale=None, shift=None, relu=False, pad_c
     o = f32[:n].view(b, ct, oh, ow)
     assert bool((o[:, :c_off] == FILL).all()) and bool((o[:, c_off + cout:] == FILL).all()), "fp32 channels outside the range written"
     mine = o[:, c_off:c_off + cout]
+    if not want_f32:
+        assert bool((mine == FILL).all()), "fp32 written by a call that did not ask for it"
+    forms = {"f32": mine if want_f32 else None, "hi": None, "lo": None}
     # planes [B, OH, OW, ct]: the hi / lo split of exactly the fp32 values, nothing else touched
-    for plane, want in ((p_hi, bf16_bits(mine)), (p_lo, None if not split else bf16_bits(mine - bits_to_f32(bf16_bits(mine))))):
+    for name, plane in (("hi", p_hi), ("lo", p_lo)):
         if plane is None:
             continue
         assert bool((plane[n:] == FILL16).all()), "plane tail written"
         pv = plane[:n].view(b, oh, ow, ct)
         assert bool((pv[..., :c_off] == FILL16).all()) and bool((pv[..., c_off + cout:] == FILL16).all()), "plane channels outside the range written"
-        assert torch.equal(pv[..., c_off:c_off + cout].permute(0, 3, 1, 2), want), "planes are not the bf16 split of the fp32 result"
-    return mine.cpu().numpy()
+        own = pv[..., c_off:c_off + cout]
+        if not want_planes:
+            assert bool((own == FILL16).all()), "planes written by a call that did not ask for them"
+            continue
+        forms[name] = own
+        if want_f32:
+            want = bf16_bits(mine) if name == "hi" else bf16_bits(mine - bits_to_f32(bf16_bits(mine)))
+            assert torch.equal(own.permute(0, 3, 1, 2), want), "planes are not the bf16 split of the fp32 result"
+    return forms
 
 
 def reference(kind, x, wt, k, s, scale, shift, relu):
@@ -139,6 +159,32 @@ def test_conv_every_size_around_the_tile(k, s, mode):
         err, bound = float(np.abs(out - ref).max()), BOUND[mode] * max(1.0, float(np.abs(ref).max()))
         print(f"conv k{k} s{s} [{h}, {w}] {mode}: err {err:.3e} bound {bound:.3e}")
         assert out.shape == ref.shape and err <= bound, (k, s, h, w, err, bound)
+
+
+# the image encoder's calls (vision_tower._conv): ONE output form, no scale / shift, no ReLU, c_in = 256 and 512 (the widest the kernel
+# takes), c_out = 512, and net_3's second half written at channel offset 512 of 1024
+TOWER_CALLS = ((256, 512, 64, 32), (512, 512, 64, 32), (512, 512, 512, 512))     # (c_in, c_out, pad_c, c_off)
+
+
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+@pytest.mark.parametrize("s", [1, 2])
+@pytest.mark.parametrize("cin,cout,pad_c,c_off", TOWER_CALLS)
+def test_conv_as_the_image_encoder_calls_it(cin, cout, pad_c, c_off, s, mode):
+    """Held to fp64 with both forms requested; then planes only and fp32 only, each bit-equal to the same form of the call for both."""
+    for i, (h, w) in enumerate(((9, 17), (16, 16))):
+        x, wt, _, _ = BC.layer_operands("conv", 2, cin, cout, 3, h, w, mode, 1300 + 10 * TOWER_CALLS.index((cin, cout, pad_c, c_off)) + i)
+        ref = BC.conv_ref(x, wt, 3, s)
+        both = run_forms("conv", x, wt, 3, s, mode, pad_c=pad_c, c_off=c_off)
+        out = both["f32"].cpu().numpy()
+        err, bound = float(np.abs(out - ref).max()), BOUND[mode] * max(1.0, float(np.abs(ref).max()))
+        print(f"conv {cin}->{cout} at {c_off} of {cout + pad_c} k3 s{s} [2, {h}, {w}] {mode}: err {err:.3e} bound {bound:.3e}")
+        assert out.shape == ref.shape and err <= bound, (cin, cout, s, h, w, mode, err, bound)
+        planes = run_forms("conv", x, wt, 3, s, mode, pad_c=pad_c, c_off=c_off, outputs="planes")
+        f32 = run_forms("conv", x, wt, 3, s, mode, pad_c=pad_c, c_off=c_off, outputs="f32")
+        assert planes["f32"] is None and f32["hi"] is None and f32["lo"] is None
+        assert torch.equal(f32["f32"].view(torch.int32), both["f32"].view(torch.int32))
+        assert torch.equal(planes["hi"], both["hi"]) and (both["lo"] is None) == (mode == "bf16")
+        assert both["lo"] is None or torch.equal(planes["lo"], both["lo"])
 
 
 @pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
