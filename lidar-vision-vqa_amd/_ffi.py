@@ -113,35 +113,50 @@ def _push(rec: dict):
     check(lib().lvq_set_tuning(ctypes.byref(t)), "lvq_set_tuning")
 
 
+_C_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
+_C_RETURNS = dict(_C_TYPES, **{"void": None, "const char *": ctypes.c_char_p})
+
+
+def prototypes(text: Optional[str] = None) -> dict:
+    """{name: (restype, [argtypes])} of every function declared in include/lvq.h (or in `text`): the header is the only statement
+    of a signature, and lib() binds every entry point from this table.  Pointers, arrays and lvq_stream_t travel as c_void_p;
+    a type outside the table raises LvqError (nothing is guessed)."""
+    if text is None:
+        with open(HEADER_PATH) as f:
+            text = f.read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(lvq_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        ret = " ".join(ret.split())
+        args = []
+        for p in (q.strip() for q in params.split(",") if q.strip() != "void"):
+            if "*" in p or "[" in p or p.split()[0] == "lvq_stream_t":
+                args.append(ctypes.c_void_p)
+            else:
+                args.append(_C_TYPES.get(" ".join(p.split()[:-1])))
+        if ret not in _C_RETURNS or None in args:
+            raise LvqError(f"include/lvq.h: no ctypes mapping for a type of `{ret} {name}({' '.join(params.split())})`")
+        out[name] = (_C_RETURNS[ret], args)
+    return out
+
+
 def declared_symbols() -> List[str]:
     """Every function name declared in include/lvq.h (used by the export test and INTEGRATION.md)."""
-    with open(HEADER_PATH) as f:
-        txt = f.read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(lvq_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(prototypes())
 
 
 def lib() -> ctypes.CDLL:
-    """Load liblvq_hip.so (built by __graft_entry__.build() / `make -C lidar-vision-vqa_amd/csrc`)."""
+    """Load liblvq_hip.so (built by __graft_entry__.build() / `make -C lidar-vision-vqa_amd/csrc`) and give every entry point the
+    argtypes / restype of its declaration in include/lvq.h: callers pass plain Python values, a wrong width is an ArgumentError."""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise LvqError(f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(hipcc --offload-arch=gfx950).  There is no CPU/PyTorch fallback for the hot path.")
         L = ctypes.CDLL(LIB_PATH)
-        L.lvq_version.restype = ctypes.c_char_p
-        L.lvq_strerror.restype = ctypes.c_char_p
-        L.lvq_strerror.argtypes = [ctypes.c_int]
-        for name in ("lvq_voxelize_hard_workspace_bytes", "lvq_voxelize_dynamic_workspace_bytes", "lvq_pillar_dwconv_workspace_bytes",
-                     "lvq_sparse_bev_merge_workspace_bytes", "lvq_sparse_to_dense_workspace_bytes", "lvq_qwen2_decode_workspace_bytes",
-                     "lvq_bev_tiles_workspace_bytes", "lvq_attention_workspace_bytes", "lvq_colsum_workspace_bytes",
-                     "lvq_attention_stream_totals_workspace_bytes", "lvq_attention_tiled_signed_workspace_bytes",
-                     "lvq_bev_tile_kv_workspace_bytes", "lvq_ca_fused_packed_bytes", "lvq_ca_fused_workspace_bytes",
-                     "lvq_attention_decode_ragged_workspace_bytes", "lvq_qwen2_decode_ragged_workspace_bytes",
-                     "lvq_attention_extend_shared_workspace_bytes", "lvq_qwen2_extend_shared_workspace_bytes",
-                     "lvq_attention_relpos_workspace_bytes"):
-            getattr(L, name).restype = ctypes.c_size_t
-        L.lvq_tuning_defaults.restype = None
+        for name, (restype, argtypes) in prototypes().items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _lib = L
         _push(tuning_from_env())               # the library itself never reads the environment (include/lvq.h: lvq_tuning)
     return _lib
@@ -172,11 +187,26 @@ def require_cuda(*tensors: torch.Tensor):
             raise LvqError("tensor must be contiguous")
 
 
+_WORKSPACES = {}
+
+
+def workspace(nbytes: int, device, tag: str, *, per_stream: bool = False, floor: int = 0) -> torch.Tensor:
+    """Grow-only scratch buffer handed to the C ABI (the library never allocates): one per (device, tag), or per (device, tag,
+    current stream) with per_stream.  Calls that share a tag share the bytes, so they must not overlap on different streams."""
+    device = torch.device(device)
+    index = device.index if device.index is not None else torch.cuda.current_device()
+    key = (index, tag, torch.cuda.current_stream(device).cuda_stream if per_stream else None)
+    buf = _WORKSPACES.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = _WORKSPACES[key] = torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=device)
+    return buf
+
+
 def attention_relpos_plan(gh: int, gw: int, precision: int):
     """lvq_attention_relpos_plan (host only, a hook for tests): (K | V stages, dynamic LDS bytes) of the kernel that the fused
     relative-position attention launches on a gh x gw grid; precision 1 = plain bf16, 3 = hi + lo."""
     stages, nbytes = ctypes.c_int(0), ctypes.c_size_t(0)
-    check(lib().lvq_attention_relpos_plan(cint(gh), cint(gw), cint(precision), ctypes.byref(stages), ctypes.byref(nbytes)),
+    check(lib().lvq_attention_relpos_plan(gh, gw, precision, ctypes.byref(stages), ctypes.byref(nbytes)),
           f"lvq_attention_relpos_plan ({gh} x {gw}, precision {precision})")
     return stages.value, nbytes.value
 

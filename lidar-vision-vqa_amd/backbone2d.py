@@ -19,7 +19,6 @@ UPSAMPLE_STRIDES below 1 become a strided conv of kernel = stride = int(round(1 
 """
 from __future__ import annotations
 
-import ctypes
 from typing import List, Optional, Tuple
 
 import torch
@@ -31,14 +30,7 @@ from . import autograd_route as AG
 MODES = ("bf16x3", "bf16")
 DEFAULT_MODE = "bf16x3"
 FAMILY = "c_in 1 .. 512, c_out a multiple of 64 in 64 .. 512; kernel 3 at stride 1 / 2, or kernel = stride in 1, 2, 4"
-
-
-def _lib():
-    L = F.lib()
-    if getattr(L.lvq_conv2d_packed_elems, "restype", None) is not ctypes.c_size_t:
-        L.lvq_conv2d_packed_elems.restype = ctypes.c_size_t
-        L.lvq_conv2d_plane_elems.restype = ctypes.c_size_t
-    return L
+_lib = F.lib
 
 
 def pad32(c: int) -> int:
@@ -59,10 +51,10 @@ def to_planes(x: torch.Tensor, split: bool) -> Planes:
     """lvq_conv2d_to_planes: [B, C, H, W] fp32 -> Planes."""
     F.require_cuda(x)
     b, c, h, w = x.shape
-    if _lib().lvq_conv2d_plane_elems(F.cint(b), F.cint(c), F.cint(h), F.cint(w)) == 0:
+    if _lib().lvq_conv2d_plane_elems(b, c, h, w) == 0:
         raise F.LvqError(f"lvq_conv2d_to_planes: a [{b}, {c}, {h}, {w}] canvas is outside the kernel family ({FAMILY})")
     p = Planes(b, h, w, c, split, x.device)
-    F.check(_lib().lvq_conv2d_to_planes(F.ptr(x), F.cint(b), F.cint(c), F.cint(h), F.cint(w), F.ptr(p.hi), F.ptr(p.lo), F.stream_ptr(x.device)),
+    F.check(_lib().lvq_conv2d_to_planes(F.ptr(x), b, c, h, w, F.ptr(p.hi), F.ptr(p.lo), F.stream_ptr(x.device)),
             "lvq_conv2d_to_planes")
     return p
 
@@ -95,14 +87,14 @@ class _Layer:
             return hit[1]
         L = _lib()
         k = self.stride if self.transposed else self.kernel
-        n = L.lvq_conv2d_packed_elems(F.cint(self.c_out), F.cint(self.c_in), F.cint(k), F.cint(int(self.transposed)))
+        n = L.lvq_conv2d_packed_elems(self.c_out, self.c_in, k, int(self.transposed))
         if n == 0:
             raise F.LvqError(f"lvq_conv2d: {type(self.conv).__name__}({self.c_in} -> {self.c_out}, kernel {self.kernel}, stride {self.stride}) is "
                              f"outside the kernel family ({FAMILY})")
         w = p.detach().float().contiguous()
         hi = torch.empty((n,), dtype=torch.int16, device=w.device)
         lo = torch.empty((n,), dtype=torch.int16, device=w.device) if split else None
-        F.check(L.lvq_conv2d_pack_weights(F.ptr(w), F.cint(self.c_out), F.cint(self.c_in), F.cint(k), F.cint(int(self.transposed)), F.ptr(hi),
+        F.check(L.lvq_conv2d_pack_weights(F.ptr(w), self.c_out, self.c_in, k, int(self.transposed), F.ptr(hi),
                                           F.ptr(lo), F.stream_ptr(w.device)), "lvq_conv2d_pack_weights")
         self._cache[("w", split)] = (ver, (hi, lo))
         return hi, lo
@@ -142,14 +134,14 @@ class _Layer:
         c_total = targets[0][2]                      # the pixel pitch of the planes = the channel count of the fp32 buffer
         if any(t != (oh, ow, c_total) for t in targets):
             raise F.LvqError(f"{type(self.conv).__name__}: output {oh} x {ow} does not fit its target(s) {targets} (h, w, channels)")
-        out = (F.ptr(planes.hi if planes is not None else None), F.ptr(planes.lo if planes is not None else None), F.ptr(f32), F.cint(c_total),
-               F.cint(c_off), F.stream_ptr(dev))
-        head = (F.ptr(x.hi), F.ptr(x.lo), F.cint(x.batch), F.cint(x.h), F.cint(x.w), F.cint(self.c_in), F.ptr(hi), F.ptr(lo), F.cint(self.c_out))
-        tail = (F.ptr(scale), F.ptr(shift), F.cint(int(self.relu)))
+        out = (F.ptr(planes.hi if planes is not None else None), F.ptr(planes.lo if planes is not None else None), F.ptr(f32), c_total,
+               c_off, F.stream_ptr(dev))
+        head = (F.ptr(x.hi), F.ptr(x.lo), x.batch, x.h, x.w, self.c_in, F.ptr(hi), F.ptr(lo), self.c_out)
+        tail = (F.ptr(scale), F.ptr(shift), int(self.relu))
         if self.transposed:
-            F.check(_lib().lvq_deconv2d(*head, F.cint(self.stride), *tail, *out), "lvq_deconv2d")
+            F.check(_lib().lvq_deconv2d(*head, self.stride, *tail, *out), "lvq_deconv2d")
         else:
-            F.check(_lib().lvq_conv2d(*head, F.cint(self.kernel), F.cint(self.stride), *tail, *out), "lvq_conv2d")
+            F.check(_lib().lvq_conv2d(*head, self.kernel, self.stride, *tail, *out), "lvq_conv2d")
         return planes
 
 

@@ -19,7 +19,6 @@ downstream addresses rows through coordinates.
 """
 from __future__ import annotations
 
-import ctypes
 from functools import partial
 from typing import Optional, Tuple
 
@@ -29,18 +28,10 @@ import torch.nn as nn
 from . import _ffi as F
 from . import autograd_route as AG
 from .bev import SparseTensor, bev_out
-from .lidar import workspace
 
 MODES = ("bf16x3", "bf16")
 DEFAULT_MODE = "bf16x3"
-
-
-def _lib():
-    L = F.lib()
-    if getattr(L.lvq_sparse_conv_rules_workspace_bytes, "restype", None) is not ctypes.c_size_t:
-        L.lvq_sparse_conv_rules_workspace_bytes.restype = ctypes.c_size_t
-        L.lvq_sparse_conv_packed_elems.restype = ctypes.c_size_t
-    return L
+_lib = F.lib
 
 
 class SparseConvTensor(SparseTensor):
@@ -74,7 +65,7 @@ def sparse_conv_rules(indices: torch.Tensor, spatial_shape, batch_size: int, ker
     for v in k:
         kvol *= v
     out_shape = shape if subm else [(d + 2 * pp - kk) // ss + 1 for d, pp, kk, ss in zip(shape, p, k, s)]
-    args = (F.cint(nd), F.i32x(shape), F.cint(batch_size), F.i32x(k), F.i32x(s), F.i32x(p), F.cint(int(subm)))
+    args = (nd, F.i32x(shape), batch_size, F.i32x(k), F.i32x(s), F.i32x(p), int(subm))
     n_out = torch.zeros((1,), dtype=torch.int32, device=dev)
     cells = batch_size
     kc = 1
@@ -84,12 +75,12 @@ def sparse_conv_rules(indices: torch.Tensor, spatial_shape, batch_size: int, ker
     full = max(1, min(n * (1 if subm else kc), cells))
     cap = full if subm else max(1, min(full, 4 * n + 64))      # LiDAR voxels reach ~2.8 sites each through a stride-2 layer
     while True:
-        nbytes = L.lvq_sparse_conv_rules_workspace_bytes(F.i64(n), *args)
-        ws = workspace(max(nbytes, 1), dev, "sprules")
+        nbytes = L.lvq_sparse_conv_rules_workspace_bytes(n, *args)
+        ws = F.workspace(nbytes, dev, "sprules", floor=1 << 20)
         out_idx = idx if subm else torch.empty((cap, cols), dtype=torch.int32, device=dev)
         nbr = torch.empty((cap, kvol), dtype=torch.int32, device=dev)
-        rc = L.lvq_sparse_conv_rules(F.ptr(idx), F.i64(n), *args, F.i64(cap), F.ptr(None if subm else out_idx), F.ptr(nbr), F.ptr(n_out),
-                                     F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+        rc = L.lvq_sparse_conv_rules(F.ptr(idx), n, *args, cap, F.ptr(None if subm else out_idx), F.ptr(nbr), F.ptr(n_out),
+                                     F.ptr(ws), ws.numel(), F.stream_ptr(dev))
         F.check(rc, "lvq_sparse_conv_rules")
         if subm:
             return idx, nbr[:n], n_out, out_shape
@@ -143,14 +134,14 @@ class _SparseConv(nn.Module):
         kvol = 1
         for k in self.kernel_size:
             kvol *= k
-        n = L.lvq_sparse_conv_packed_elems(F.cint(self.out_channels), F.cint(kvol), F.cint(self.in_channels))
+        n = L.lvq_sparse_conv_packed_elems(self.out_channels, kvol, self.in_channels)
         if n == 0:
             raise F.LvqError(f"lvq_sparse_conv: channels ({self.in_channels} -> {self.out_channels}) outside the kernel family "
                              "(C_in in 4, 5, 16, 32, 64, 128; C_out in 16, 32, 64, 128)")
         w = p.detach().float().contiguous()
         hi = torch.empty((n,), dtype=torch.int16, device=w.device)
         lo = torch.empty((n,), dtype=torch.int16, device=w.device) if split else None
-        F.check(L.lvq_sparse_conv_pack_weights(F.ptr(w), F.cint(self.out_channels), F.cint(kvol), F.cint(self.in_channels), F.ptr(hi), F.ptr(lo),
+        F.check(L.lvq_sparse_conv_pack_weights(F.ptr(w), self.out_channels, kvol, self.in_channels, F.ptr(hi), F.ptr(lo),
                                                F.stream_ptr(w.device)), "lvq_sparse_conv_pack_weights")
         self._cache[("w", split)] = (ver, (hi, lo))
         return hi, lo
@@ -211,9 +202,9 @@ class _SparseConv(nn.Module):
             residual = residual.contiguous()
             assert residual.shape == out.shape and residual.dtype == torch.float32
         if m:
-            rc = _lib().lvq_sparse_conv(F.ptr(feats), F.i64(feats.shape[0]), F.cint(self.in_channels), F.ptr(nbr), F.cint(kvol), F.i64(m),
-                                        F.ptr(None), F.ptr(hi), F.ptr(lo), F.cint(self.out_channels), F.ptr(bias), F.ptr(scale), F.ptr(shift),
-                                        F.ptr(residual), F.cint(int(relu)), F.ptr(out), F.stream_ptr(feats.device))
+            rc = _lib().lvq_sparse_conv(F.ptr(feats), feats.shape[0], self.in_channels, F.ptr(nbr), kvol, m,
+                                        F.ptr(None), F.ptr(hi), F.ptr(lo), self.out_channels, F.ptr(bias), F.ptr(scale), F.ptr(shift),
+                                        F.ptr(residual), int(relu), F.ptr(out), F.stream_ptr(feats.device))
             F.check(rc, "lvq_sparse_conv")
         return SparseConvTensor(out, rec["out_indices"], rec["out_shape"], x.batch_size, x.indice_dict, x.precision)
 

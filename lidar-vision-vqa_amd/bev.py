@@ -21,7 +21,6 @@ import torch
 import torch.nn as nn
 
 from . import _ffi as F
-from .lidar import workspace
 
 
 # --------------------------------------------------------------------------------------------------
@@ -64,7 +63,7 @@ def f16_to_f32(src: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     F.require_cuda(src)
     assert src.dtype == torch.float16
     out = out if out is not None else torch.empty(src.shape, dtype=torch.float32, device=src.device)
-    F.check(F.lib().lvq_f16_to_f32(F.ptr(src), F.ptr(out), F.i64(src.numel()), F.stream_ptr(src.device)), "lvq_f16_to_f32")
+    F.check(F.lib().lvq_f16_to_f32(F.ptr(src), F.ptr(out), src.numel(), F.stream_ptr(src.device)), "lvq_f16_to_f32")
     return out
 
 
@@ -135,9 +134,9 @@ class SparseTensor:
         h, w = self.spatial_shape[-2], self.spatial_shape[-1]
         out = torch.empty((self.batch_size, c * d, h, w), dtype=torch.float32, device=feats.device)
         L = F.lib()
-        ws = workspace(L.lvq_sparse_to_dense_workspace_bytes(F.cint(self.batch_size), F.cint(d), F.cint(h), F.cint(w)), feats.device, "dense")
-        rc = L.lvq_sparse_to_dense(F.ptr(feats), F.ptr(idx), F.cint(nd + 1), F.i64(m), F.ptr(None), F.cint(c),
-                                   F.cint(self.batch_size), F.cint(d), F.cint(h), F.cint(w), F.ptr(out), F.ptr(ws), F.csize(ws.numel()),
+        ws = F.workspace(L.lvq_sparse_to_dense_workspace_bytes(self.batch_size, d, h, w), feats.device, "dense", floor=1 << 20)
+        rc = L.lvq_sparse_to_dense(F.ptr(feats), F.ptr(idx), nd + 1, m, F.ptr(None), c,
+                                   self.batch_size, d, h, w, F.ptr(out), F.ptr(ws), ws.numel(),
                                    F.stream_ptr(feats.device))
         F.check(rc, "lvq_sparse_to_dense")
         return out.view(self.batch_size, c, d, h, w) if nd == 3 else out
@@ -153,17 +152,17 @@ def bev_out(x_conv: SparseTensor) -> SparseTensor:
     ny, nx = x_conv.spatial_shape[1], x_conv.spatial_shape[2]
     dev = feats.device
     L = F.lib()
-    nbytes = L.lvq_sparse_bev_merge_workspace_bytes(F.i64(m), F.cint(x_conv.batch_size), F.cint(ny), F.cint(nx))
+    nbytes = L.lvq_sparse_bev_merge_workspace_bytes(m, x_conv.batch_size, ny, nx)
     if nbytes == 0:
         raise F.LvqError("lvq_sparse_bev_merge: batch * ny * nx must stay below 2^31")
-    ws = workspace(nbytes, dev, "bevmerge")
+    ws = F.workspace(nbytes, dev, "bevmerge", floor=1 << 20)
     cap = max(1, min(m, x_conv.batch_size * ny * nx))
     out_idx = torch.empty((cap, 3), dtype=torch.int32, device=dev)
     out_feats = torch.empty((cap, c), dtype=torch.float32, device=dev)
     inv = torch.empty((max(m, 1),), dtype=torch.int32, device=dev)
     counts = torch.zeros((2,), dtype=torch.int32, device=dev)
-    rc = L.lvq_sparse_bev_merge(F.ptr(idx), F.ptr(feats), F.i64(m), F.cint(c), F.cint(x_conv.batch_size), F.cint(ny), F.cint(nx),
-                                F.ptr(out_idx), F.ptr(out_feats), F.ptr(inv), F.ptr(counts), F.ptr(ws), F.csize(ws.numel()),
+    rc = L.lvq_sparse_bev_merge(F.ptr(idx), F.ptr(feats), m, c, x_conv.batch_size, ny, nx,
+                                F.ptr(out_idx), F.ptr(out_feats), F.ptr(inv), F.ptr(counts), F.ptr(ws), ws.numel(),
                                 F.stream_ptr(dev))
     F.check(rc, "lvq_sparse_bev_merge")
     m2 = int(counts[0].item())            # the reference's torch.unique synchronises here as well

@@ -858,17 +858,15 @@ def sdp_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, attn_mask: 
     qb, kb, vb = (ops.cast(_f32(t).view(B * H * t.shape[2], D), split) for t in (q, k, v))
     bias = None if attn_mask is None else _f32(attn_mask.expand(B, H, S, Sk))
     # output addressed as [B, S, H*D] by the ABI; request [B,H,S,D] through the strides instead
-    import ctypes
     oh, ol = ops._bf_empty((B * H * S, D), q.device, split)
     L = F.lib()
-    L.lvq_attention_workspace_bytes.restype = ctypes.c_size_t
-    nbytes = L.lvq_attention_workspace_bytes(F.cint(B), F.cint(H), F.cint(S), F.cint(Sk), F.cint(D), F.cint(3 if split else 1))
+    nbytes = L.lvq_attention_workspace_bytes(B, H, S, Sk, D, 3 if split else 1)
     ws = torch.empty(int(nbytes), dtype=torch.uint8, device=q.device)
     rc = L.lvq_attention_bf16(F.ptr(qb[0]), F.ptr(qb[1]), F.ptr(kb[0]), F.ptr(kb[1]), F.ptr(vb[0]), F.ptr(vb[1]), F.ptr(bias),
-                              F.cint(B), F.cint(H), F.cint(H), F.cint(S), F.cint(Sk), F.cint(D),
-                              F.i64(H * S * D), F.i64(D), F.i64(S * D), F.i64(H * Sk * D), F.i64(D), F.i64(Sk * D),
-                              F.i64(H * Sk * D), F.i64(D), F.i64(Sk * D), F.i64(H * S * D), F.i64(D), F.i64(S * D),
-                              F.cfloat(1.0 / math.sqrt(D)), F.cint(0), F.ptr(oh), F.ptr(ol), F.ptr(ws), F.csize(ws.numel()),
+                              B, H, H, S, Sk, D,
+                              H * S * D, D, S * D, H * Sk * D, D, Sk * D,
+                              H * Sk * D, D, Sk * D, H * S * D, D, S * D,
+                              1.0 / math.sqrt(D), 0, F.ptr(oh), F.ptr(ol), F.ptr(ws), ws.numel(),
                               F.stream_ptr(q.device))
     F.check(rc, "lvq_attention_bf16")
     return ops.to_f32((oh, ol)).view(B, H, S, D)

@@ -312,11 +312,11 @@ class StandInHead(_HipModule):
     def _extend_shared(self, layers_arr, prefix_arr, prefix, pidx, rows, B, lq, own0, qn, t, lown, prec, ws):
         """lvq_qwen2_extend_shared on rows [B * lq, d] fp32, in place: sequence b continues prefix pidx[b] behind own0[b] + t own rows."""
         c = self.cfg
-        rc = F.lib().lvq_qwen2_extend_shared(layers_arr, prefix_arr, F.cint(len(self.model.layers)), F.ptr(rows), F.cint(B), F.cint(lq),
-                                             F.cint(c["d"]), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.ptr(pidx),
-                                             F.ptr(prefix.plen), F.cint(prefix.n_prefix), F.cint(prefix.pmax), F.ptr(own0), F.ptr(qn), F.cint(t),
-                                             F.cint(lown), F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec), F.ptr(ws),
-                                             F.csize(ws.numel()), F.stream_ptr(rows.device))
+        rc = F.lib().lvq_qwen2_extend_shared(layers_arr, prefix_arr, len(self.model.layers), F.ptr(rows), B, lq,
+                                             c["d"], c["n_heads"], c["n_kv_heads"], c["inter"], F.ptr(pidx),
+                                             F.ptr(prefix.plen), prefix.n_prefix, prefix.pmax, F.ptr(own0), F.ptr(qn), t,
+                                             lown, c["rms_eps"], c["rope_theta"], prec, F.ptr(ws),
+                                             ws.numel(), F.stream_ptr(rows.device))
         F.check(rc, "lvq_qwen2_extend_shared")
 
     @torch.no_grad()
@@ -386,9 +386,9 @@ class StandInHead(_HipModule):
             for i, ((kh, kl), (vh, vl)) in enumerate(prefix.layers):
                 prefix_arr[i] = _Qwen2PrefixPtrs(kh.data_ptr(), None if kl is None else kl.data_ptr(), vh.data_ptr(),
                                                  None if vl is None else vl.data_ptr())
-            nbytes = max(int(lib.lvq_qwen2_extend_shared_workspace_bytes(F.cint(B), F.cint(lq), F.cint(d), F.cint(c["n_heads"]),
-                                                                         F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(prefix.pmax),
-                                                                         F.cint(lmax), F.cint(prec))) for lq in (L, 1))
+            nbytes = max(int(lib.lvq_qwen2_extend_shared_workspace_bytes(B, lq, d, c["n_heads"],
+                                                                         c["n_kv_heads"], c["inter"], prefix.pmax,
+                                                                         lmax, prec)) for lq in (L, 1))
             step_ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
             zeros, ones = torch.zeros(B, dtype=torch.int32, device=dev), torch.ones(B, dtype=torch.int32, device=dev)
             extend = lambda rows, lq, own0, qn, t: self._extend_shared(layers_arr, prefix_arr, prefix, pidx, rows, B, lq, own0, qn, t, lmax,
@@ -401,7 +401,7 @@ class StandInHead(_HipModule):
             layers_arr, keep = self._native_layers(cache)
             prec = 3 if split else 1
             ws_query = lib.lvq_qwen2_decode_ragged_workspace_bytes if ragged else lib.lvq_qwen2_decode_workspace_bytes
-            nbytes = ws_query(F.cint(B), F.cint(d), F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(lmax), F.cint(prec))
+            nbytes = ws_query(B, d, c["n_heads"], c["n_kv_heads"], c["inter"], lmax, prec)
             step_ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
         if ragged or shared:                                   # last real row of every sequence
             last = x.view(B, L, d)[torch.arange(B, device=dev), pos0.long() - 1].contiguous()
@@ -428,16 +428,16 @@ class StandInHead(_HipModule):
             if shared:                                         # sequence b: own row qlen[b] + t, one query row (csrc/decode_shared.hip)
                 extend(x, 1, qlen, ones, t)
             elif ragged:                                         # sequence b at position pos0[b] + t (csrc/decode_ragged.hip)
-                rc = lib.lvq_qwen2_decode_step_ragged(layers_arr, F.cint(len(self.model.layers)), F.ptr(x), F.cint(B), F.cint(d),
-                                                      F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.ptr(pos0), F.cint(t),
-                                                      F.cint(lmax), F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec),
-                                                      F.ptr(step_ws), F.csize(step_ws.numel()), F.stream_ptr(dev))
+                rc = lib.lvq_qwen2_decode_step_ragged(layers_arr, len(self.model.layers), F.ptr(x), B, d,
+                                                      c["n_heads"], c["n_kv_heads"], c["inter"], F.ptr(pos0), t,
+                                                      lmax, c["rms_eps"], c["rope_theta"], prec,
+                                                      F.ptr(step_ws), step_ws.numel(), F.stream_ptr(dev))
                 F.check(rc, "lvq_qwen2_decode_step_ragged")
             elif native:
-                rc = lib.lvq_qwen2_decode_step(layers_arr, F.cint(len(self.model.layers)), F.ptr(x), F.cint(B), F.cint(d),
-                                               F.cint(c["n_heads"]), F.cint(c["n_kv_heads"]), F.cint(c["inter"]), F.cint(L + t), F.cint(lmax),
-                                               F.cfloat(c["rms_eps"]), F.cfloat(c["rope_theta"]), F.cint(prec), F.ptr(step_ws),
-                                               F.csize(step_ws.numel()), F.stream_ptr(dev))
+                rc = lib.lvq_qwen2_decode_step(layers_arr, len(self.model.layers), F.ptr(x), B, d,
+                                               c["n_heads"], c["n_kv_heads"], c["inter"], L + t, lmax,
+                                               c["rms_eps"], c["rope_theta"], prec, F.ptr(step_ws),
+                                               step_ws.numel(), F.stream_ptr(dev))
                 F.check(rc, "lvq_qwen2_decode_step")
             else:
                 x = self._layers(x, B, 1, L + t, cache)

@@ -17,27 +17,13 @@ module in train() mode raises.
 """
 from __future__ import annotations
 
-import ctypes
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _ffi as F
-
-_WS: Dict[Tuple[int, str], torch.Tensor] = {}
-
-
-def workspace(nbytes: int, device: torch.device, tag: str = "vox") -> torch.Tensor:
-    """Grow-only per-device scratch buffer handed to the C ABI (the library never allocates)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(), tag)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
-        _WS[key] = buf
-    return buf
-
 
 def grid_size_from(point_cloud_range, voxel_size) -> np.ndarray:
     """data_processor.py:135-136."""
@@ -49,7 +35,7 @@ def mask_points_by_range(points: torch.Tensor, limit_range) -> torch.Tensor:
     F.require_cuda(points)
     n, c = points.shape
     keep = torch.empty(n, dtype=torch.uint8, device=points.device)
-    rc = F.lib().lvq_mask_points_by_range(F.ptr(points), F.i64(n), F.cint(c), F.f32x(list(limit_range)), F.ptr(keep),
+    rc = F.lib().lvq_mask_points_by_range(F.ptr(points), n, c, F.f32x(list(limit_range)), F.ptr(keep),
                                           F.stream_ptr(points.device))
     F.check(rc, "lvq_mask_points_by_range")
     return keep.bool()
@@ -87,13 +73,13 @@ class VoxelGeneratorWrapper:
         num = torch.empty((cap,), dtype=torch.int32, device=dev)
         svo = torch.empty((n_scenes + 1,), dtype=torch.int32, device=dev)
         L = F.lib()
-        nbytes = L.lvq_voxelize_hard_workspace_bytes(F.i64(n), F.cint(n_scenes))
-        ws = workspace(nbytes, dev, getattr(self, "ws_tag", "vox"))      # generators that run on different streams need their own
-        rc = L.lvq_voxelize_hard(F.ptr(points), F.ptr(scene_off), F.i64(n), F.cint(n_scenes), F.cint(c),
+        nbytes = L.lvq_voxelize_hard_workspace_bytes(n, n_scenes)
+        ws = F.workspace(nbytes, dev, getattr(self, "ws_tag", "vox"), floor=1 << 20)      # generators that run on different streams need their own
+        rc = L.lvq_voxelize_hard(F.ptr(points), F.ptr(scene_off), n, n_scenes, c,
                                  F.f32x(self.range), F.f32x(self.vsize), F.i32x(self.grid.tolist()),
-                                 F.cint(self.t), F.cint(self.max_voxels), F.cint(int(self.break_on_cap)),
-                                 F.i64(cap), F.ptr(voxels), F.ptr(coords), F.ptr(num), F.ptr(svo),
-                                 F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+                                 self.t, self.max_voxels, int(self.break_on_cap),
+                                 cap, F.ptr(voxels), F.ptr(coords), F.ptr(num), F.ptr(svo),
+                                 F.ptr(ws), ws.numel(), F.stream_ptr(dev))
         F.check(rc, "lvq_voxelize_hard")
         return voxels, coords, num, svo
 
@@ -114,11 +100,11 @@ class VoxelGeneratorWrapper:
             coords = torch.empty((cap, 4), dtype=torch.int32, device=dev)
             num = torch.empty((cap,), dtype=torch.int32, device=dev)
             svo = torch.empty((n_scenes + 1,), dtype=torch.int32, device=dev)
-            nbytes = L.lvq_voxelize_hard_workspace_bytes(F.i64(n), F.cint(n_scenes))
-            ws = workspace(nbytes, dev, getattr(self, "ws_tag", "vox"))
-            rc = L.lvq_voxelize_mean(F.ptr(points), F.ptr(scene_off), F.i64(n), F.cint(n_scenes), F.cint(c), F.f32x(self.range),
-                                     F.f32x(self.vsize), F.i32x(self.grid.tolist()), F.cint(self.t), F.cint(self.max_voxels),
-                                     F.i64(cap), F.ptr(feats), F.ptr(coords), F.ptr(num), F.ptr(svo), F.ptr(ws), F.csize(ws.numel()),
+            nbytes = L.lvq_voxelize_hard_workspace_bytes(n, n_scenes)
+            ws = F.workspace(nbytes, dev, getattr(self, "ws_tag", "vox"), floor=1 << 20)
+            rc = L.lvq_voxelize_mean(F.ptr(points), F.ptr(scene_off), n, n_scenes, c, F.f32x(self.range),
+                                     F.f32x(self.vsize), F.i32x(self.grid.tolist()), self.t, self.max_voxels,
+                                     cap, F.ptr(feats), F.ptr(coords), F.ptr(num), F.ptr(svo), F.ptr(ws), ws.numel(),
                                      F.stream_ptr(dev))
             if rc != F.LVQ_EUNSUPPORTED:       # unsupported shape: fall through to the two-call route
                 F.check(rc, "lvq_voxelize_mean")
@@ -192,7 +178,7 @@ class MeanVFE(VFETemplate):
         F.require_cuda(voxels, num)
         m, t, c = voxels.shape
         out = torch.empty((m, c), dtype=torch.float32, device=voxels.device)
-        rc = F.lib().lvq_mean_vfe(F.ptr(voxels), F.ptr(num), F.i64(m), F.ptr(n_live), F.cint(t), F.cint(c), F.ptr(out),
+        rc = F.lib().lvq_mean_vfe(F.ptr(voxels), F.ptr(num), m, F.ptr(n_live), t, c, F.ptr(out),
                                   F.stream_ptr(voxels.device))
         F.check(rc, "lvq_mean_vfe")
         return out
@@ -289,8 +275,8 @@ class PillarVFE(_PFNStack):
         m, t, c = voxels.shape
         keep, wp, sp, hp, cin, cout, flags, c_last = self._abi_layers()
         out = torch.empty((m, c_last), dtype=torch.float32, device=voxels.device)
-        rc = F.lib().lvq_pillar_vfe(F.ptr(voxels), F.ptr(num), F.ptr(coords), F.i64(m), F.ptr(n_live), F.cint(t), F.cint(c),
-                                    F.cint(len(self.pfn_layers)), wp, sp, hp, cin, cout, F.cint(flags),
+        rc = F.lib().lvq_pillar_vfe(F.ptr(voxels), F.ptr(num), F.ptr(coords), m, F.ptr(n_live), t, c,
+                                    len(self.pfn_layers), wp, sp, hp, cin, cout, flags,
                                     F.f32x([self.voxel_x, self.voxel_y, self.voxel_z]),
                                     F.f32x([self.x_offset, self.y_offset, self.z_offset]), F.ptr(out),
                                     F.stream_ptr(voxels.device))
@@ -324,13 +310,13 @@ def _dynamic_voxelize(points: torch.Tensor, batch_size: int, pcr, vsize, grid, n
     counts = torch.empty((2,), dtype=torch.int32, device=dev)
     L = F.lib()
     gi = F.i32x(g)
-    nbytes = L.lvq_voxelize_dynamic_workspace_bytes(F.i64(n), F.cint(batch_size), gi, F.cint(ndim))
+    nbytes = L.lvq_voxelize_dynamic_workspace_bytes(n, batch_size, gi, ndim)
     if nbytes == 0:
         F.check(-4, "lvq_voxelize_dynamic (batch_size * grid cells must stay below 2^31)")
-    ws = workspace(nbytes, dev)
-    rc = L.lvq_voxelize_dynamic(F.ptr(pts), F.i64(n), F.cint(c), F.cint(batch_size), F.f32x([float(np.float32(v)) for v in pcr]),
-                                F.f32x([float(np.float32(v)) for v in vsize]), gi, F.cint(ndim), F.ptr(inv), F.ptr(pc),
-                                F.ptr(key), F.ptr(cnt), F.ptr(coords), F.ptr(counts), F.ptr(ws), F.csize(ws.numel()),
+    ws = F.workspace(nbytes, dev, "vox", floor=1 << 20)
+    rc = L.lvq_voxelize_dynamic(F.ptr(pts), n, c, batch_size, F.f32x([float(np.float32(v)) for v in pcr]),
+                                F.f32x([float(np.float32(v)) for v in vsize]), gi, ndim, F.ptr(inv), F.ptr(pc),
+                                F.ptr(key), F.ptr(cnt), F.ptr(coords), F.ptr(counts), F.ptr(ws), ws.numel(),
                                 F.stream_ptr(dev))
     F.check(rc, "lvq_voxelize_dynamic")
     return dict(pts=pts, inv=inv, pt_coords=pc, unq_key=key, unq_cnt=cnt, coords=coords, counts=counts, cap=cap)
@@ -340,8 +326,8 @@ def _scatter_mean(dv, col0: int, nc: int) -> torch.Tensor:
     pts = dv["pts"]
     n, c = pts.shape
     sums = torch.zeros((dv["cap"], nc), dtype=torch.float32, device=pts.device)
-    rc = F.lib().lvq_scatter_mean(F.ptr(pts), F.i64(n), F.cint(c), F.cint(col0), F.cint(nc), F.ptr(dv["inv"]),
-                                  F.ptr(dv["unq_cnt"]), F.i64(dv["cap"]), F.ptr(sums), F.ptr(sums), F.stream_ptr(pts.device))
+    rc = F.lib().lvq_scatter_mean(F.ptr(pts), n, c, col0, nc, F.ptr(dv["inv"]),
+                                  F.ptr(dv["unq_cnt"]), dv["cap"], F.ptr(sums), F.ptr(sums), F.stream_ptr(pts.device))
     F.check(rc, "lvq_scatter_mean")
     return sums
 
@@ -395,8 +381,8 @@ class _DynamicPFN(_PFNStack):
         out = torch.zeros((cap, c_last), dtype=torch.float32, device=pts.device)
         nl = len(self.pfn_layers)
         tmp = torch.zeros((cap, self.pfn_layers[0].cout), dtype=torch.float32, device=pts.device) if nl == 2 else None
-        rc = F.lib().lvq_dynamic_pfn(F.ptr(pts), F.i64(n), F.cint(c), F.ptr(dv["inv"]), F.ptr(dv["pt_coords"]), F.ptr(mean),
-                                     F.cint(self.KIND), F.cint(nl), wp, sp, hp, cin, cout, F.cint(flags),
+        rc = F.lib().lvq_dynamic_pfn(F.ptr(pts), n, c, F.ptr(dv["inv"]), F.ptr(dv["pt_coords"]), F.ptr(mean),
+                                     self.KIND, nl, wp, sp, hp, cin, cout, flags,
                                      F.f32x([self.voxel_x, self.voxel_y, self.voxel_z]),
                                      F.f32x([self.x_offset, self.y_offset, self.z_offset]), F.ptr(tmp), F.ptr(out),
                                      F.stream_ptr(pts.device))
@@ -469,8 +455,8 @@ class PointPillarScatter(nn.Module):
         assert ch == self.num_bev_features
         canvas = out if out is not None else torch.empty((batch_size, ch * self.nz, self.ny, self.nx), dtype=torch.float32,
                                                          device=feats.device)
-        rc = F.lib().lvq_pillar_scatter(F.ptr(feats), F.ptr(coords), F.i64(m), F.ptr(n_live), F.cint(ch), F.cint(batch_size),
-                                        F.cint(self.ny), F.cint(self.nx), F.ptr(canvas), F.stream_ptr(feats.device))
+        rc = F.lib().lvq_pillar_scatter(F.ptr(feats), F.ptr(coords), m, F.ptr(n_live), ch, batch_size,
+                                        self.ny, self.nx, F.ptr(canvas), F.stream_ptr(feats.device))
         F.check(rc, "lvq_pillar_scatter")
         return canvas
 
@@ -496,4 +482,4 @@ __all__ = {
     "DynamicVoxelVFE": DynamicVoxelVFE,
 }
 map_to_bev_all = {"PointPillarScatter": PointPillarScatter}
-from . import bev as _bev  # noqa: E402,F401  (bev.py ends by adding "HeightCompression" here: it imports `workspace` from this module, so it cannot be named above)
+from . import bev as _bev  # noqa: E402,F401  (bev.py ends by adding "HeightCompression" here)

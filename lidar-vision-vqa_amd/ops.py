@@ -72,14 +72,14 @@ def cast(x: torch.Tensor, split: bool) -> BF:
     F.require_cuda(x)
     assert x.dtype == torch.float32
     hi, lo = _bf_empty(x.shape, x.device, split)
-    F.check(F.lib().lvq_cast_bf16(F.ptr(x), F.i64(x.numel()), F.ptr(hi), F.ptr(lo), F.stream_ptr(x.device)), "lvq_cast_bf16")
+    F.check(F.lib().lvq_cast_bf16(F.ptr(x), x.numel(), F.ptr(hi), F.ptr(lo), F.stream_ptr(x.device)), "lvq_cast_bf16")
     return hi, lo
 
 
 def to_f32(x: BF, alpha: float = 1.0) -> torch.Tensor:
     hi, lo = x
     out = torch.empty(hi.shape, dtype=torch.float32, device=hi.device)
-    F.check(F.lib().lvq_bf16_to_f32(F.ptr(hi), F.ptr(lo), F.i64(hi.numel()), F.cfloat(alpha), F.ptr(out),
+    F.check(F.lib().lvq_bf16_to_f32(F.ptr(hi), F.ptr(lo), hi.numel(), alpha, F.ptr(out),
                                     F.stream_ptr(hi.device)), "lvq_bf16_to_f32")
     return out
 
@@ -92,9 +92,9 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor]
     rows, d = x.shape
     y32 = torch.empty_like(x) if want_f32 else None
     hi, lo = _bf_empty(x.shape, x.device, split) if want_bf else (None, None)
-    rc = F.lib().lvq_layernorm(F.ptr(x), F.ptr(add), F.cint(add.shape[0] if add is not None else 0), F.cint(add_group),
-                               F.ptr(gamma), F.ptr(beta), F.cfloat(eps), F.i64(rows), F.cint(d), F.ptr(post),
-                               F.i64(post.shape[0] if post is not None else 0), F.ptr(y32), F.ptr(hi), F.ptr(lo),
+    rc = F.lib().lvq_layernorm(F.ptr(x), F.ptr(add), add.shape[0] if add is not None else 0, add_group,
+                               F.ptr(gamma), F.ptr(beta), eps, rows, d, F.ptr(post),
+                               post.shape[0] if post is not None else 0, F.ptr(y32), F.ptr(hi), F.ptr(lo),
                                F.stream_ptr(x.device))
     F.check(rc, "lvq_layernorm")
     return y32, ((hi, lo) if want_bf else None)
@@ -103,7 +103,7 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor]
 def rmsnorm(x: torch.Tensor, gamma: torch.Tensor, eps: float, split: bool) -> BF:
     rows, d = x.shape
     hi, lo = _bf_empty(x.shape, x.device, split)
-    rc = F.lib().lvq_rmsnorm(F.ptr(x), F.ptr(gamma), F.cfloat(eps), F.i64(rows), F.cint(d), F.ptr(None), F.ptr(hi), F.ptr(lo),
+    rc = F.lib().lvq_rmsnorm(F.ptr(x), F.ptr(gamma), eps, rows, d, F.ptr(None), F.ptr(hi), F.ptr(lo),
                              F.stream_ptr(x.device))
     F.check(rc, "lvq_rmsnorm")
     return hi, lo
@@ -125,19 +125,15 @@ def linear(a: BF, w: BF, bias: Optional[torch.Tensor] = None, *, gelu: bool = Fa
     ch, cl = _bf_empty((m, n), dev, al is not None) if out_bf else (None, None)
     wo = r0 * k * 2  # byte offset of the weight row slice
     bo = r0 * 4
-    import ctypes
     with region(tag, dev):
         rc = F.lib().lvq_gemm_bf16(
-            F.ptr(ah), F.ptr(al), ctypes.c_void_p(wh.data_ptr() + wo), ctypes.c_void_p(wl.data_ptr() + wo if split else 0),
-            ctypes.c_void_p(bias.data_ptr() + bo if bias is not None else 0), F.ptr(residual), F.ptr(rowtab),
-            F.i64(rowtab.shape[0] if rowtab is not None else 0), F.cfloat(alpha), F.cint(1 if gelu else 0), F.i64(m), F.cint(n),
-            F.cint(k), F.i64(k), F.i64(k), F.i64(n), F.cint(1), F.i64(0), F.i64(0), F.i64(0), F.ptr(c32), F.ptr(ch), F.ptr(cl),
+            F.ptr(ah), F.ptr(al), wh.data_ptr() + wo, wl.data_ptr() + wo if split else None,
+            bias.data_ptr() + bo if bias is not None else None, F.ptr(residual), F.ptr(rowtab),
+            rowtab.shape[0] if rowtab is not None else 0, alpha, 1 if gelu else 0, m, n,
+            k, k, k, n, 1, 0, 0, 0, F.ptr(c32), F.ptr(ch), F.ptr(cl),
             F.stream_ptr(dev))
     F.check(rc, f"lvq_gemm_bf16 (m={m}, n={n}, k={k})")
     return c32, ((ch, cl) if out_bf else None)
-
-
-_ATT_WS = {}
 
 
 def attention(q: BF, k: BF, v: BF, *, batch: int, n_heads: int, n_kv_heads: int, nq: int, nkv: int, dh: int,
@@ -145,37 +141,31 @@ def attention(q: BF, k: BF, v: BF, *, batch: int, n_heads: int, n_kv_heads: int,
               tag: Optional[str] = None) -> BF:
     """q/k/v: BF views (possibly column slices of packed projections); *_strides = (batch, row, head) in elements.
     Returns BF [batch*nq, n_heads*dh]."""
-    import ctypes
     qh, ql = q
     dev = qh.device
     split = ql is not None                       # q split, k / v plain = the "mixed" stream form (lvq_attention_stream_ok shapes)
     oh, ol = _bf_empty((batch * nq, n_heads * dh), dev, split)
     L = F.lib()
-    L.lvq_attention_workspace_bytes.restype = ctypes.c_size_t
-    nbytes = L.lvq_attention_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(nq), F.cint(nkv), F.cint(dh),
-                                             F.cint(3 if k[1] is not None else 1))
-    key = (dev.index, "attn")
-    ws = _ATT_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _ATT_WS[key] = ws
+    nbytes = L.lvq_attention_workspace_bytes(batch, n_heads, nq, nkv, dh,
+                                             3 if k[1] is not None else 1)
+    ws = F.workspace(nbytes, dev, "attn")
     d = n_heads * dh
     with region(tag, dev):
         rc = L.lvq_attention_bf16(
-            F.ptr(qh), F.ptr(ql), F.ptr(k[0]), F.ptr(k[1]), F.ptr(v[0]), F.ptr(v[1]), F.ptr(bias), F.cint(batch), F.cint(n_heads),
-            F.cint(n_kv_heads), F.cint(nq), F.cint(nkv), F.cint(dh),
-            F.i64(q_strides[0]), F.i64(q_strides[1]), F.i64(q_strides[2]),
-            F.i64(k_strides[0]), F.i64(k_strides[1]), F.i64(k_strides[2]),
-            F.i64(v_strides[0]), F.i64(v_strides[1]), F.i64(v_strides[2]),
-            F.i64(nq * d), F.i64(d), F.i64(dh), F.cfloat(scale), F.cint(1 if causal else 0), F.ptr(oh), F.ptr(ol),
-            F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+            F.ptr(qh), F.ptr(ql), F.ptr(k[0]), F.ptr(k[1]), F.ptr(v[0]), F.ptr(v[1]), F.ptr(bias), batch, n_heads,
+            n_kv_heads, nq, nkv, dh,
+            q_strides[0], q_strides[1], q_strides[2],
+            k_strides[0], k_strides[1], k_strides[2],
+            v_strides[0], v_strides[1], v_strides[2],
+            nq * d, d, dh, scale, 1 if causal else 0, F.ptr(oh), F.ptr(ol),
+            F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_bf16 (B={batch}, H={n_heads}, nq={nq}, nkv={nkv}, dh={dh})")
     return oh, ol
 
 
 def attention_relpos_ok(gh: int, gw: int, dh: int) -> bool:
     """lvq_attention_relpos_ok: the fused grid attention with decomposed relative-position bias takes (gh, gw, dh)."""
-    return bool(F.lib().lvq_attention_relpos_ok(F.cint(gh), F.cint(gw), F.cint(dh)))
+    return bool(F.lib().lvq_attention_relpos_ok(gh, gw, dh))
 
 
 def attention_relpos(qkv: BF, rel_h: BF, rel_w: BF, *, batch: int, n_heads: int, gh: int, gw: int, dh: int, scale: float,
@@ -191,12 +181,12 @@ def attention_relpos(qkv: BF, rel_h: BF, rel_w: BF, *, batch: int, n_heads: int,
                          f"fit batch {batch}, grid {gh} x {gw}, head dim {dh}")
     oh, ol = _bf_empty((batch * gh * gw, n_heads * dh), dev, split)
     L = F.lib()
-    nbytes = L.lvq_attention_relpos_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(gh), F.cint(gw), F.cint(dh), F.cint(3 if split else 1))
-    ws = _att_ws(dev, int(nbytes)) if nbytes else None
+    nbytes = L.lvq_attention_relpos_workspace_bytes(batch, n_heads, gh, gw, dh, 3 if split else 1)
+    ws = F.workspace(nbytes, dev, "attn") if nbytes else None
     with region(tag, dev):
-        rc = L.lvq_attention_relpos_bf16(F.ptr(qh), F.ptr(ql), F.i64(qh.shape[1]), F.ptr(rel_h[0]), F.ptr(rel_h[1]), F.ptr(rel_w[0]),
-                                         F.ptr(rel_w[1]), F.cint(batch), F.cint(n_heads), F.cint(gh), F.cint(gw), F.cint(dh), F.cfloat(scale),
-                                         F.ptr(oh), F.ptr(ol), F.i64(n_heads * dh), F.ptr(ws), F.csize(ws.numel() if ws is not None else 0),
+        rc = L.lvq_attention_relpos_bf16(F.ptr(qh), F.ptr(ql), qh.shape[1], F.ptr(rel_h[0]), F.ptr(rel_h[1]), F.ptr(rel_w[0]),
+                                         F.ptr(rel_w[1]), batch, n_heads, gh, gw, dh, scale,
+                                         F.ptr(oh), F.ptr(ol), n_heads * dh, F.ptr(ws), ws.numel() if ws is not None else 0,
                                          F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_relpos_bf16 (B={batch}, H={n_heads}, grid {gh} x {gw}, dh={dh})")
     return oh, ol
@@ -214,21 +204,17 @@ def attention_decode_ragged(q: BF, k_cache: BF, v_cache: BF, kv_len: torch.Tenso
     split = ql is not None
     oh, ol = _bf_empty((batch, n_heads * dh), dev, split)
     L = F.lib()
-    nbytes = L.lvq_attention_decode_ragged_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(n_kv_heads), F.cint(lmax), F.cint(dh),
-                                                           F.cint(3 if split else 1))
-    key = (dev.index, "attn_ragged")
-    ws = _ATT_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _ATT_WS[key] = ws
+    nbytes = L.lvq_attention_decode_ragged_workspace_bytes(batch, n_heads, n_kv_heads, lmax, dh,
+                                                           3 if split else 1)
+    ws = F.workspace(nbytes, dev, "attn_ragged")
     d = n_heads * dh
     rc = L.lvq_attention_decode_ragged(
-        F.ptr(qh), F.ptr(ql), F.ptr(k_cache[0]), F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(kv_len), F.cint(batch),
-        F.cint(n_heads), F.cint(n_kv_heads), F.cint(lmax), F.cint(dh),
-        F.i64(q_strides[0]), F.i64(q_strides[1]), F.i64(q_strides[2]),
-        F.i64(k_strides[0]), F.i64(k_strides[1]), F.i64(k_strides[2]),
-        F.i64(v_strides[0]), F.i64(v_strides[1]), F.i64(v_strides[2]),
-        F.i64(d), F.i64(d), F.i64(dh), F.cfloat(scale), F.ptr(oh), F.ptr(ol), F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+        F.ptr(qh), F.ptr(ql), F.ptr(k_cache[0]), F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(kv_len), batch,
+        n_heads, n_kv_heads, lmax, dh,
+        q_strides[0], q_strides[1], q_strides[2],
+        k_strides[0], k_strides[1], k_strides[2],
+        v_strides[0], v_strides[1], v_strides[2],
+        d, d, dh, scale, F.ptr(oh), F.ptr(ol), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_decode_ragged (B={batch}, H={n_heads}, Hkv={n_kv_heads}, lmax={lmax}, dh={dh})")
     return oh, ol
 
@@ -253,27 +239,23 @@ def attention_extend_shared(q: BF, pk_cache: BF, pv_cache: BF, k_cache: BF, v_ca
     F.require_cuda(qh, ql, *pk_cache, *pv_cache, *k_cache, *v_cache)
     oh, ol = _bf_empty((batch, lq, d), dev, split)
     L = F.lib()
-    nbytes = L.lvq_attention_extend_shared_workspace_bytes(F.cint(batch), F.cint(lq), F.cint(n_heads), F.cint(n_kv_heads), F.cint(pmax),
-                                                           F.cint(lown), F.cint(dh), F.cint(3 if split else 1))
-    key = (dev.index, "attn_shared")
-    ws = _ATT_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-        _ATT_WS[key] = ws
+    nbytes = L.lvq_attention_extend_shared_workspace_bytes(batch, lq, n_heads, n_kv_heads, pmax,
+                                                           lown, dh, 3 if split else 1)
+    ws = F.workspace(nbytes, dev, "attn_shared")
     rc = L.lvq_attention_extend_shared(
         F.ptr(qh), F.ptr(ql), F.ptr(pk_cache[0]), F.ptr(pk_cache[1]), F.ptr(pv_cache[0]), F.ptr(pv_cache[1]), F.ptr(k_cache[0]),
-        F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(prefix_index), F.ptr(plen), F.ptr(own0), F.ptr(qn), F.cint(batch),
-        F.cint(lq), F.cint(n_heads), F.cint(n_kv_heads), F.cint(n_prefix), F.cint(pmax), F.cint(lown), F.cint(dh),
-        F.i64(lq * d), F.i64(d), F.i64(dh), F.i64(pmax * dkv), F.i64(lown * dkv), F.i64(dkv), F.i64(dh),
-        F.i64(pmax * dkv), F.i64(lown * dkv), F.i64(dkv), F.i64(dh), F.i64(lq * d), F.i64(d), F.i64(dh), F.cfloat(scale), F.ptr(oh), F.ptr(ol),
-        F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+        F.ptr(k_cache[1]), F.ptr(v_cache[0]), F.ptr(v_cache[1]), F.ptr(prefix_index), F.ptr(plen), F.ptr(own0), F.ptr(qn), batch,
+        lq, n_heads, n_kv_heads, n_prefix, pmax, lown, dh,
+        lq * d, d, dh, pmax * dkv, lown * dkv, dkv, dh,
+        pmax * dkv, lown * dkv, dkv, dh, lq * d, d, dh, scale, F.ptr(oh), F.ptr(ol),
+        F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_extend_shared (B={batch}, lq={lq}, H={n_heads}, Hkv={n_kv_heads}, G={n_prefix}, pmax={pmax}, lown={lown}, dh={dh})")
     return oh, ol
 
 
 def ca_fused_ok(batch: int, nq: int, nkv: int, d: int, n_heads: int) -> bool:
     """Shapes of the fused short-K/V cross-attention kernel (include/lvq.h: lvq_ca_fused_ok)."""
-    return bool(F.lib().lvq_ca_fused_ok(F.cint(batch), F.cint(nq), F.cint(nkv), F.cint(d), F.cint(n_heads)))
+    return bool(F.lib().lvq_ca_fused_ok(batch, nq, nkv, d, n_heads))
 
 
 def ca_fused_pack(ln_w: torch.Tensor, ln_b: torch.Tensor, in_w: torch.Tensor, in_b: torch.Tensor, out_w: torch.Tensor, out_b: torch.Tensor,
@@ -282,12 +264,12 @@ def ca_fused_pack(ln_w: torch.Tensor, ln_b: torch.Tensor, in_w: torch.Tensor, in
     F.require_cuda(ln_w, ln_b, in_w, in_b, out_w, out_b)
     d = out_w.shape[0]
     L = F.lib()
-    nbytes = int(L.lvq_ca_fused_packed_bytes(F.cint(d), F.cint(n_heads)))
+    nbytes = int(L.lvq_ca_fused_packed_bytes(d, n_heads))
     if nbytes == 0:
         raise F.LvqError(f"lvq_ca_fused: d={d}, heads={n_heads} is not a shape of the fused kernel")
     blob = torch.empty(nbytes, dtype=torch.uint8, device=out_w.device)
-    rc = L.lvq_ca_fused_pack(F.ptr(ln_w), F.ptr(ln_b), F.ptr(in_w), F.ptr(in_b), F.ptr(out_w), F.ptr(out_b), F.cint(d), F.cint(n_heads),
-                             F.cint(1 if f16 else 0), F.ptr(blob), F.csize(nbytes), F.stream_ptr(out_w.device))
+    rc = L.lvq_ca_fused_pack(F.ptr(ln_w), F.ptr(ln_b), F.ptr(in_w), F.ptr(in_b), F.ptr(out_w), F.ptr(out_b), d, n_heads,
+                             1 if f16 else 0, F.ptr(blob), nbytes, F.stream_ptr(out_w.device))
     F.check(rc, "lvq_ca_fused_pack")
     return blob
 
@@ -299,25 +281,21 @@ def ca_fused(q: torch.Tensor, kv: torch.Tensor, blob: torch.Tensor, eps: float, 
     nkv = kv.shape[1]
     dev = q.device
     L = F.lib()
-    nbytes = int(L.lvq_ca_fused_workspace_bytes(F.cint(B), F.cint(nq), F.cint(nkv), F.cint(d), F.cint(n_heads)))
+    nbytes = int(L.lvq_ca_fused_workspace_bytes(B, nq, nkv, d, n_heads))
     if nbytes == 0:
         raise F.LvqError(f"lvq_ca_fused: (B={B}, nq={nq}, nkv={nkv}, d={d}, heads={n_heads}) is not a shape of the fused kernel")
-    key = (dev.index, "ca_fused")
-    ws = _ATT_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _ATT_WS[key] = ws
+    ws = F.workspace(nbytes, dev, "ca_fused")
     out = torch.empty_like(q)
     with region(tag, dev):
-        rc = L.lvq_ca_fused(F.ptr(q), F.ptr(kv), F.ptr(blob), F.cfloat(eps), F.cint(B), F.cint(nq), F.cint(nkv), F.cint(d), F.cint(n_heads),
-                            F.cint(1 if f16 else 0), F.ptr(out), F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+        rc = L.lvq_ca_fused(F.ptr(q), F.ptr(kv), F.ptr(blob), eps, B, nq, nkv, d, n_heads,
+                            1 if f16 else 0, F.ptr(out), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_ca_fused (B={B}, nq={nq}, nkv={nkv})")
     return out
 
 
 def attention_stream_ok(nq: int, nkv: int, dh: int) -> bool:
     """True when lvq_attention_bf16 takes (q split, k / v plain) for this shape: the long-stream kernel's shapes."""
-    return bool(F.lib().lvq_attention_stream_ok(F.cint(nq), F.cint(nkv), F.cint(dh)))
+    return bool(F.lib().lvq_attention_stream_ok(nq, nkv, dh))
 
 
 def bev_occupied_cells(bev: torch.Tensor, cap: Optional[int] = None):
@@ -329,7 +307,7 @@ def bev_occupied_cells(bev: torch.Tensor, cap: Optional[int] = None):
     feats = torch.empty((cap, C), dtype=torch.float32, device=bev.device)
     coords = torch.empty((cap, 4), dtype=torch.int32, device=bev.device)
     n = torch.empty(1, dtype=torch.int32, device=bev.device)
-    rc = F.lib().lvq_bev_occupied_cells(F.ptr(bev), F.cint(B), F.cint(C), F.cint(H), F.cint(W), F.i64(cap), F.ptr(feats), F.ptr(coords), F.ptr(n),
+    rc = F.lib().lvq_bev_occupied_cells(F.ptr(bev), B, C, H, W, cap, F.ptr(feats), F.ptr(coords), F.ptr(n),
                                         F.stream_ptr(bev.device))
     F.check(rc, "lvq_bev_occupied_cells")
     return feats, coords, n
@@ -340,13 +318,10 @@ def dwconv3x3_gelu(bev: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor]
     F.require_cuda(bev, w, b)
     B, C, H, W = bev.shape
     hi, lo = _bf_empty((B * H * W, C), bev.device, split)
-    rc = F.lib().lvq_dwconv3x3_gelu(F.ptr(bev), F.ptr(w), F.ptr(b), F.cint(B), F.cint(C), F.cint(H), F.cint(W), F.ptr(hi),
+    rc = F.lib().lvq_dwconv3x3_gelu(F.ptr(bev), F.ptr(w), F.ptr(b), B, C, H, W, F.ptr(hi),
                                     F.ptr(lo), F.stream_ptr(bev.device))
     F.check(rc, "lvq_dwconv3x3_gelu")
     return hi, lo
-
-
-_PD_WS = {}
 
 
 def pillar_dwconv3x3_gelu(feat: torch.Tensor, coords: torch.Tensor, n_live: Optional[torch.Tensor], batch: int, ny: int, nx: int,
@@ -357,15 +332,10 @@ def pillar_dwconv3x3_gelu(feat: torch.Tensor, coords: torch.Tensor, n_live: Opti
     m, C = feat.shape
     hi, lo = _bf_empty((batch * ny * nx, C), feat.device, split)
     L = F.lib()
-    nbytes = int(L.lvq_pillar_dwconv_workspace_bytes(F.cint(batch), F.cint(ny), F.cint(nx)))
-    key = feat.device.index if feat.device.index is not None else torch.cuda.current_device()
-    ws = _PD_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
-        _PD_WS[key] = ws
-    import ctypes
-    rc = L.lvq_pillar_dwconv3x3_gelu(F.ptr(feat), F.ptr(coords), F.i64(m), F.ptr(n_live), F.cint(C), F.cint(batch), F.cint(ny), F.cint(nx),
-                                     F.ptr(w), F.ptr(b), F.ptr(hi), F.ptr(lo), F.ptr(ws), ctypes.c_size_t(ws.numel()), F.stream_ptr(feat.device))
+    nbytes = int(L.lvq_pillar_dwconv_workspace_bytes(batch, ny, nx))
+    ws = F.workspace(nbytes, feat.device, "pillar_dwconv")
+    rc = L.lvq_pillar_dwconv3x3_gelu(F.ptr(feat), F.ptr(coords), m, F.ptr(n_live), C, batch, ny, nx,
+                                     F.ptr(w), F.ptr(b), F.ptr(hi), F.ptr(lo), F.ptr(ws), ws.numel(), F.stream_ptr(feat.device))
     F.check(rc, "lvq_pillar_dwconv3x3_gelu")
     return hi, lo
 
@@ -375,13 +345,10 @@ def pillar_index_map(coords: torch.Tensor, n_live: Optional[torch.Tensor], batch
     """[batch, ny, nx] int32: pillar row or -1 (PointPillarScatter as an index map)."""
     F.require_cuda(coords, n_live)
     idx = torch.empty((batch, ny, nx), dtype=torch.int32, device=coords.device)
-    rc = F.lib().lvq_pillar_index_map(F.ptr(coords), F.i64(coords.shape[0]), F.ptr(n_live), F.cint(batch), F.cint(ny), F.cint(nx), F.ptr(idx),
+    rc = F.lib().lvq_pillar_index_map(F.ptr(coords), coords.shape[0], F.ptr(n_live), batch, ny, nx, F.ptr(idx),
                                       F.stream_ptr(coords.device))
     F.check(rc, "lvq_pillar_index_map")
     return idx
-
-
-_TILE_WS = {}
 
 
 def bev_tiles(idx: Optional[torch.Tensor], batch: int, ny: int, nx: int, device, row_base: int, force_all: bool = False):
@@ -394,14 +361,10 @@ def bev_tiles(idx: Optional[torch.Tensor], batch: int, ny: int, nx: int, device,
     src = torch.empty((batch, ny * nx), dtype=torch.int32, device=device)
     counts = torch.empty((3,), dtype=torch.int32, device=device)
     L = F.lib()
-    nbytes = int(L.lvq_bev_tiles_workspace_bytes(F.cint(batch), F.cint(ny), F.cint(nx)))
-    key = (torch.device(device).index, torch.cuda.current_stream(device).cuda_stream)
-    ws = _TILE_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        _TILE_WS[key] = ws
-    rc = L.lvq_bev_tiles(F.ptr(idx), F.cint(batch), F.cint(ny), F.cint(nx), F.cint(1 if force_all else 0), F.cint(row_base), F.ptr(live), F.ptr(dirty),
-                         F.ptr(src), F.ptr(counts), F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(device))
+    nbytes = int(L.lvq_bev_tiles_workspace_bytes(batch, ny, nx))
+    ws = F.workspace(nbytes, device, "bev_tiles", per_stream=True)
+    rc = L.lvq_bev_tiles(F.ptr(idx), batch, ny, nx, 1 if force_all else 0, row_base, F.ptr(live), F.ptr(dirty),
+                         F.ptr(src), F.ptr(counts), F.ptr(ws), ws.numel(), F.stream_ptr(device))
     F.check(rc, "lvq_bev_tiles")
     return live, dirty, src, counts
 
@@ -415,9 +378,9 @@ def bev_tile_tokens(feat: torch.Tensor, idx: torch.Tensor, live: torch.Tensor, d
     n = w[0].shape[0]
     xh, xl = _bf_empty((cap_rows, n), feat.device, out_lo)
     with region(tag, feat.device):
-        rc = F.lib().lvq_bev_tile_tokens(F.ptr(feat), F.ptr(idx), F.ptr(live), F.ptr(dirty), F.ptr(counts), F.i64(batch * (ny // 8) * (nx // 8)), F.cint(batch),
-                                         F.cint(ny), F.cint(nx), F.cint(feat.shape[1]), F.ptr(w9), F.ptr(b9), F.ptr(w[0]), F.ptr(w[1]), F.ptr(bias),
-                                         F.ptr(gamma), F.ptr(beta), F.cfloat(eps), F.ptr(pe_tiled), F.cint(n), F.ptr(xh), F.ptr(xl),
+        rc = F.lib().lvq_bev_tile_tokens(F.ptr(feat), F.ptr(idx), F.ptr(live), F.ptr(dirty), F.ptr(counts), batch * (ny // 8) * (nx // 8), batch,
+                                         ny, nx, feat.shape[1], F.ptr(w9), F.ptr(b9), F.ptr(w[0]), F.ptr(w[1]), F.ptr(bias),
+                                         F.ptr(gamma), F.ptr(beta), eps, F.ptr(pe_tiled), n, F.ptr(xh), F.ptr(xl),
                                          F.stream_ptr(feat.device))
     F.check(rc, "lvq_bev_tile_tokens")
     return xh, xl
@@ -439,18 +402,14 @@ def bev_tile_kv(feat: torch.Tensor, idx: torch.Tensor, live: torch.Tensor, dirty
     cap_tiles = batch * (ny // 8) * (nx // 8)
     ws = None
     if split_launch:
-        nbytes = int(L.lvq_bev_tile_kv_workspace_bytes(F.i64(cap_tiles)))
-        key = (feat.device.index, "tile_kv", torch.cuda.current_stream(feat.device).cuda_stream)
-        ws = _TILE_WS.get(key)
-        if ws is None or ws.numel() < nbytes:
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=feat.device)
-            _TILE_WS[key] = ws
+        nbytes = int(L.lvq_bev_tile_kv_workspace_bytes(cap_tiles))
+        ws = F.workspace(nbytes, feat.device, "tile_kv", per_stream=True)
     with region(tag, feat.device):
-        rc = L.lvq_bev_tile_kv(F.ptr(feat), F.ptr(idx), F.ptr(live), F.ptr(dirty), F.ptr(counts), F.i64(cap_tiles), F.cint(batch),
-                               F.cint(ny), F.cint(nx), F.cint(feat.shape[1]), F.ptr(w9), F.ptr(b9), F.ptr(m[0]), F.ptr(m[1]), F.ptr(m0), F.ptr(r[0]),
-                               F.ptr(r[1]), F.ptr(r0), F.cfloat(c0), F.cint(d_ln), F.cfloat(eps), F.ptr(t_tiled), F.cint(1 if t_f16 else 0), F.cint(n2 // 2),
-                               F.cint(1 if k_fp16 else 0), F.ptr(out),
-                               F.ptr(ws), F.csize(ws.numel() if ws is not None else 0), F.stream_ptr(feat.device))
+        rc = L.lvq_bev_tile_kv(F.ptr(feat), F.ptr(idx), F.ptr(live), F.ptr(dirty), F.ptr(counts), cap_tiles, batch,
+                               ny, nx, feat.shape[1], F.ptr(w9), F.ptr(b9), F.ptr(m[0]), F.ptr(m[1]), F.ptr(m0), F.ptr(r[0]),
+                               F.ptr(r[1]), F.ptr(r0), c0, d_ln, eps, F.ptr(t_tiled), 1 if t_f16 else 0, n2 // 2,
+                               1 if k_fp16 else 0, F.ptr(out),
+                               F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(feat.device))
     F.check(rc, "lvq_bev_tile_kv")
     return out
 
@@ -459,7 +418,6 @@ def linear_live_rows(a: BF, w: BF, bias: Optional[torch.Tensor], rows_dev: torch
                      out: Optional[torch.Tensor] = None) -> BF:
     """a [cap, k] @ w[r0:r1].T + bias over the first *rows_dev rows (device-side count) -> BF [cap, n] (hi only unless a is split).
     `out` (plain bf16 [>= cap, n], contiguous): write there instead of a fresh buffer."""
-    import ctypes
     ah, al = a
     wh, wl = w
     cap, k = ah.shape
@@ -473,10 +431,10 @@ def linear_live_rows(a: BF, w: BF, bias: Optional[torch.Tensor], rows_dev: torch
         ch, cl = _bf_empty((cap, n), ah.device, al is not None)
     wo, bo = r0 * k * 2, r0 * 4
     with region(tag, ah.device):
-        rc = F.lib().lvq_gemm_bf16_live_rows(F.ptr(ah), F.ptr(al), ctypes.c_void_p(wh.data_ptr() + wo),
-                                             ctypes.c_void_p(wl.data_ptr() + wo if wl is not None else 0),
-                                             ctypes.c_void_p(bias.data_ptr() + bo if bias is not None else 0), F.i64(cap), F.ptr(rows_dev), F.cint(n),
-                                             F.cint(k), F.i64(k), F.i64(k), F.i64(n), F.ptr(ch), F.ptr(cl), F.stream_ptr(ah.device))
+        rc = F.lib().lvq_gemm_bf16_live_rows(F.ptr(ah), F.ptr(al), wh.data_ptr() + wo,
+                                             wl.data_ptr() + wo if wl is not None else None,
+                                             bias.data_ptr() + bo if bias is not None else None, cap, F.ptr(rows_dev), n,
+                                             k, k, k, n, F.ptr(ch), F.ptr(cl), F.stream_ptr(ah.device))
     F.check(rc, f"lvq_gemm_bf16_live_rows (cap={cap}, n={n}, k={k})")
     return ch, cl
 
@@ -490,24 +448,15 @@ def attention_tiled(q: BF, kv: torch.Tensor, row_src: torch.Tensor, *, batch: in
     d = n_heads * dh
     oh, ol = _bf_empty((batch * nq, d), dev, ql is not None)
     L = F.lib()
-    nbytes = int(L.lvq_attention_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(nq), F.cint(n_tiles * 64), F.cint(dh), F.cint(1)))
-    ws = _att_ws(dev, nbytes)
+    nbytes = int(L.lvq_attention_workspace_bytes(batch, n_heads, nq, n_tiles * 64, dh, 1))
+    ws = F.workspace(nbytes, dev, "attn")
     with region(tag, dev):
-        rc = L.lvq_attention_bf16_tiled(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.ptr(row_src), F.cint(batch), F.cint(n_heads), F.cint(nq),
-                                        F.cint(n_tiles), F.cint(dh), F.i64(nq * d), F.i64(d), F.i64(dh), F.i64(2 * d), F.i64(dh), F.i64(nq * d), F.i64(d),
-                                        F.i64(dh), F.cfloat(scale), F.cint(1 if k_fp16 else 0), F.ptr(oh), F.ptr(ol), F.ptr(ws), F.csize(ws.numel()),
+        rc = L.lvq_attention_bf16_tiled(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.ptr(row_src), batch, n_heads, nq,
+                                        n_tiles, dh, nq * d, d, dh, 2 * d, dh, nq * d, d,
+                                        dh, scale, 1 if k_fp16 else 0, F.ptr(oh), F.ptr(ol), F.ptr(ws), ws.numel(),
                                         F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_bf16_tiled (B={batch}, H={n_heads}, nq={nq}, tiles={n_tiles})")
     return oh, ol
-
-
-def _att_ws(dev, nbytes: int) -> torch.Tensor:
-    key = (dev.index, "attn")
-    ws = _ATT_WS.get(key)
-    if ws is None or ws.numel() < nbytes:
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        _ATT_WS[key] = ws
-    return ws
 
 
 def attention_stream_totals(q: BF, kv: torch.Tensor, *, n_heads: int, nq: int, nkv: int, dh: int, scale: float, k_fp16: int = 0) -> torch.Tensor:
@@ -517,13 +466,13 @@ def attention_stream_totals(q: BF, kv: torch.Tensor, *, n_heads: int, nq: int, n
     dev = qh.device
     d = n_heads * dh
     L = F.lib()
-    nbytes = int(L.lvq_attention_stream_totals_workspace_bytes(F.cint(n_heads), F.cint(nq), F.cint(nkv), F.cint(dh)))
+    nbytes = int(L.lvq_attention_stream_totals_workspace_bytes(n_heads, nq, nkv, dh))
     if nbytes == 0:
         raise F.LvqError(f"attention_stream_totals: shape (nq={nq}, nkv={nkv}, dh={dh}) is not a long-stream shape")
-    ws = _att_ws(dev, nbytes)
+    ws = F.workspace(nbytes, dev, "attn")
     tot = torch.empty((n_heads, nq, dh + 2), dtype=torch.float32, device=dev)
-    rc = L.lvq_attention_bf16_stream_totals(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.cint(n_heads), F.cint(nq), F.cint(nkv), F.cint(dh),
-                                            F.i64(d), F.i64(dh), F.i64(2 * d), F.i64(dh), F.cfloat(scale), F.cint(int(k_fp16)), F.ptr(tot), F.ptr(ws), F.csize(ws.numel()),
+    rc = L.lvq_attention_bf16_stream_totals(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), n_heads, nq, nkv, dh,
+                                            d, dh, 2 * d, dh, scale, int(k_fp16), F.ptr(tot), F.ptr(ws), ws.numel(),
                                             F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_bf16_stream_totals (H={n_heads}, nq={nq}, nkv={nkv})")
     return tot
@@ -534,7 +483,7 @@ def bev_scene_pairs(row_src: torch.Tensor, batch: int, n_tiles: int, row_base: i
     dev = row_src.device
     pair_src = torch.empty((batch, n_tiles, 64), dtype=torch.int32, device=dev)
     pair_info = torch.empty((batch, 2), dtype=torch.int32, device=dev)
-    rc = F.lib().lvq_bev_scene_pairs(F.ptr(row_src), F.cint(batch), F.cint(n_tiles), F.cint(row_base), F.cint(n_tiles), F.ptr(pair_src),
+    rc = F.lib().lvq_bev_scene_pairs(F.ptr(row_src), batch, n_tiles, row_base, n_tiles, F.ptr(pair_src),
                                      F.ptr(pair_info), F.stream_ptr(dev))
     F.check(rc, "lvq_bev_scene_pairs")
     return pair_src, pair_info
@@ -549,15 +498,15 @@ def attention_tiled_signed(q: BF, kv: torch.Tensor, row_src: torch.Tensor, pair_
     d = n_heads * dh
     oh, ol = _bf_empty((batch * nq, d), dev, ql is not None)
     L = F.lib()
-    nbytes = int(L.lvq_attention_tiled_signed_workspace_bytes(F.cint(batch), F.cint(n_heads), F.cint(nq), F.cint(n_tiles), F.cint(dh)))
+    nbytes = int(L.lvq_attention_tiled_signed_workspace_bytes(batch, n_heads, nq, n_tiles, dh))
     if nbytes == 0:
         raise F.LvqError(f"attention_tiled_signed: shape (nq={nq}, tiles={n_tiles}, dh={dh}) is not a long-stream shape")
-    ws = _att_ws(dev, nbytes)
+    ws = F.workspace(nbytes, dev, "attn")
     with region(tag, dev):
-        rc = L.lvq_attention_bf16_tiled_signed(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.ptr(row_src), F.ptr(pair_src), F.ptr(pair_info), F.cint(pair_src.shape[1]), F.ptr(totals),
-                                               F.cint(batch), F.cint(n_heads), F.cint(nq), F.cint(n_tiles), F.cint(dh),
-                                               F.i64(0 if shared_q else nq * d), F.i64(d), F.i64(dh), F.i64(2 * d), F.i64(dh), F.i64(nq * d), F.i64(d),
-                                               F.i64(dh), F.cfloat(scale), F.cint(1 if k_fp16 else 0), F.ptr(oh), F.ptr(ol), F.ptr(stats), F.ptr(ws), F.csize(ws.numel()), F.stream_ptr(dev))
+        rc = L.lvq_attention_bf16_tiled_signed(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.ptr(row_src), F.ptr(pair_src), F.ptr(pair_info), pair_src.shape[1], F.ptr(totals),
+                                               batch, n_heads, nq, n_tiles, dh,
+                                               0 if shared_q else nq * d, d, dh, 2 * d, dh, nq * d, d,
+                                               dh, scale, 1 if k_fp16 else 0, F.ptr(oh), F.ptr(ol), F.ptr(stats), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_attention_bf16_tiled_signed (B={batch}, H={n_heads}, nq={nq}, tiles={n_tiles})")
     return oh, ol
 
@@ -571,12 +520,11 @@ def stream_guard(q_hi: torch.Tensor, k_rows: torch.Tensor, n_heads: int, scale: 
     nq, nkv = q_hi.shape[0], k_rows.shape[0]
     dev = q_hi.device
     L = F.lib()
-    L.lvq_stream_guard_workspace_bytes.restype = F.csize
-    nbytes = int(L.lvq_stream_guard_workspace_bytes(F.cint(nq), F.i64(nkv)))
+    nbytes = int(L.lvq_stream_guard_workspace_bytes(nq, nkv))
     ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)          # once per weights version: not cached
     g = torch.empty((n_heads, nq), dtype=torch.float32, device=dev)
-    rc = L.lvq_stream_guard(F.ptr(q_hi), F.ptr(k_rows), F.cint(n_heads), F.cint(nq), F.i64(nkv), F.i64(q_hi.stride(0)), F.i64(k_rows.stride(0)),
-                            F.cfloat(scale), F.ptr(g), F.ptr(ws), F.csize(nbytes), F.stream_ptr(dev))
+    rc = L.lvq_stream_guard(F.ptr(q_hi), F.ptr(k_rows), n_heads, nq, nkv, q_hi.stride(0), k_rows.stride(0),
+                            scale, F.ptr(g), F.ptr(ws), nbytes, F.stream_ptr(dev))
     F.check(rc, "lvq_stream_guard")
     return g
 
@@ -585,8 +533,8 @@ def scale_add_rows(x: torch.Tensor, add: Optional[torch.Tensor], alpha: float = 
     F.require_cuda(x, add)
     rows, d = x.shape
     out = torch.empty_like(x)
-    rc = F.lib().lvq_scale_add_rows(F.ptr(x), F.ptr(add), F.i64(add.shape[0] if add is not None else 0), F.cfloat(alpha),
-                                    F.i64(rows), F.cint(d), F.ptr(out), F.stream_ptr(x.device))
+    rc = F.lib().lvq_scale_add_rows(F.ptr(x), F.ptr(add), add.shape[0] if add is not None else 0, alpha,
+                                    rows, d, F.ptr(out), F.stream_ptr(x.device))
     F.check(rc, "lvq_scale_add_rows")
     return out
 
@@ -595,12 +543,12 @@ def rope_inplace(x: BF, rows: int, seq_len: int, n_heads: int, dh: int, ld: int,
     """Rotary embedding applied in place to a (column slice of a) packed projection; position = pos0 + row % seq_len."""
     hi, lo = x
     if pos0:
-        rc = F.lib().lvq_rope_inplace_at(F.ptr(hi), F.ptr(lo), F.i64(rows), F.cint(seq_len), F.cint(pos0), F.cint(n_heads), F.cint(dh),
-                                         F.i64(ld), F.cfloat(theta), F.stream_ptr(hi.device))
+        rc = F.lib().lvq_rope_inplace_at(F.ptr(hi), F.ptr(lo), rows, seq_len, pos0, n_heads, dh,
+                                         ld, theta, F.stream_ptr(hi.device))
         F.check(rc, "lvq_rope_inplace_at")
         return
-    rc = F.lib().lvq_rope_inplace(F.ptr(hi), F.ptr(lo), F.i64(rows), F.cint(seq_len), F.cint(n_heads), F.cint(dh), F.i64(ld),
-                                  F.cfloat(theta), F.stream_ptr(hi.device))
+    rc = F.lib().lvq_rope_inplace(F.ptr(hi), F.ptr(lo), rows, seq_len, n_heads, dh, ld,
+                                  theta, F.stream_ptr(hi.device))
     F.check(rc, "lvq_rope_inplace")
 
 
@@ -609,7 +557,7 @@ def argmax_rows(x: torch.Tensor) -> torch.Tensor:
     F.require_cuda(x)
     rows, n = x.shape
     out = torch.empty((rows,), dtype=torch.int64, device=x.device)
-    F.check(F.lib().lvq_argmax_rows(F.ptr(x), F.i64(rows), F.cint(n), F.ptr(out), F.stream_ptr(x.device)), "lvq_argmax_rows")
+    F.check(F.lib().lvq_argmax_rows(F.ptr(x), rows, n, F.ptr(out), F.stream_ptr(x.device)), "lvq_argmax_rows")
     return out
 
 
@@ -620,7 +568,7 @@ def sample_rows(logits: torch.Tensor, temperature: float, top_k: int, top_p: flo
     rows, n = logits.shape
     u = torch.rand((rows,), dtype=torch.float32, device=logits.device, generator=generator)
     out = torch.empty((rows,), dtype=torch.int64, device=logits.device)
-    rc = F.lib().lvq_sample_rows(F.ptr(logits), F.i64(rows), F.cint(n), F.cfloat(temperature), F.cint(int(top_k or 0)), F.cfloat(top_p),
+    rc = F.lib().lvq_sample_rows(F.ptr(logits), rows, n, temperature, int(top_k or 0), top_p,
                                  F.ptr(u), F.ptr(out), F.stream_ptr(logits.device))
     F.check(rc, f"lvq_sample_rows (vocab={n}, top_k={top_k}: the top-k filter may only be disabled for vocab <= 1024)")
     return out
@@ -629,7 +577,7 @@ def sample_rows(logits: torch.Tensor, temperature: float, top_k: int, top_p: flo
 def swiglu(gate_up: torch.Tensor, split: bool) -> BF:
     rows, two_i = gate_up.shape
     hi, lo = _bf_empty((rows, two_i // 2), gate_up.device, split)
-    rc = F.lib().lvq_swiglu(F.ptr(gate_up), F.i64(rows), F.cint(two_i // 2), F.ptr(hi), F.ptr(lo), F.stream_ptr(gate_up.device))
+    rc = F.lib().lvq_swiglu(F.ptr(gate_up), rows, two_i // 2, F.ptr(hi), F.ptr(lo), F.stream_ptr(gate_up.device))
     F.check(rc, "lvq_swiglu")
     return hi, lo
 
@@ -638,7 +586,7 @@ def cross_entropy(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     """Mean CE over labels >= 0 (ignore_index -100): returns a 0-dim device tensor, no host sync."""
     rows, vocab = logits.shape
     acc = torch.zeros(2, dtype=torch.float32, device=logits.device)
-    rc = F.lib().lvq_cross_entropy(F.ptr(logits), F.ptr(labels), F.i64(rows), F.cint(vocab), F.ptr(acc), F.stream_ptr(logits.device))
+    rc = F.lib().lvq_cross_entropy(F.ptr(logits), F.ptr(labels), rows, vocab, F.ptr(acc), F.stream_ptr(logits.device))
     F.check(rc, "lvq_cross_entropy")
     return acc[0] / acc[1]
 
@@ -661,8 +609,8 @@ def linear_ln(a: BF, w: BF, bias: Optional[torch.Tensor], gamma: torch.Tensor, b
     split = al is not None
     yh, yl = _bf_empty((m, n), ah.device, split if out_lo is None else (out_lo and split))
     with region(tag, ah.device):
-        rc = F.lib().lvq_gemm_ln_bf16(F.ptr(ah), F.ptr(al), F.ptr(wh), F.ptr(wl), F.ptr(bias), F.ptr(gamma), F.ptr(beta), F.cfloat(eps),
-                                      F.ptr(post), F.i64(post.shape[0] if post is not None else 0), F.i64(m), F.cint(n), F.cint(k),
-                                      F.i64(k), F.i64(k), F.ptr(yh), F.ptr(yl), F.stream_ptr(ah.device))
+        rc = F.lib().lvq_gemm_ln_bf16(F.ptr(ah), F.ptr(al), F.ptr(wh), F.ptr(wl), F.ptr(bias), F.ptr(gamma), F.ptr(beta), eps,
+                                      F.ptr(post), post.shape[0] if post is not None else 0, m, n, k,
+                                      k, k, F.ptr(yh), F.ptr(yl), F.stream_ptr(ah.device))
     F.check(rc, f"lvq_gemm_ln_bf16 (m={m}, n={n}, k={k})")
     return yh, yl

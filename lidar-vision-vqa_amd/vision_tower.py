@@ -284,21 +284,16 @@ class Block(nn.Module):
         return self._run(x.float().reshape(-1, d).contiguous(), b, gh, gw, split).view(b, gh, gw, d)
 
 
-def _conv_lib():
-    from . import backbone2d
-    return backbone2d._lib()
-
-
 def _conv(conv: nn.Conv2d, x: O.BF, b: int, h: int, w: int, split: bool, planes: bool):
     """One bias-free 3 x 3 nn.Conv2d (padding 1, stride 1 or 2) on channels-last operand planes x [b * h * w, c_in]: lvq_conv2d per
     chunk of at most 512 output channels, written at its channel offset.  Returns (planes BF [b * oh * ow, c_out] | fp32 [b, c_out, oh, ow], oh, ow)."""
-    L = _conv_lib()
+    L = F.lib()
     k, s, c_in, c_out = conv.kernel_size[0], conv.stride[0], conv.in_channels, conv.out_channels
     if (tuple(conv.kernel_size), tuple(conv.padding), tuple(conv.dilation), conv.groups) != ((3, 3), (1, 1), (1, 1), 1) or conv.bias is not None \
             or tuple(conv.stride) not in ((1, 1), (2, 2)) or c_in % 32 or c_out % 64:
         raise F.LvqError(f"lvq_conv2d: Conv2d({c_in} -> {c_out}, kernel {tuple(conv.kernel_size)}, stride {tuple(conv.stride)}) is outside the "
                          "kernel family (3 x 3, padding 1, stride 1 / 2, no bias, c_in a multiple of 32, c_out of 64)")
-    oh, ow = L.lvq_conv2d_out_size(F.cint(h), F.cint(k), F.cint(s)), L.lvq_conv2d_out_size(F.cint(w), F.cint(k), F.cint(s))
+    oh, ow = L.lvq_conv2d_out_size(h, k, s), L.lvq_conv2d_out_size(w, k, s)
     dev = x[0].device
     out_bf = O._bf_empty((b * oh * ow, c_out), dev, split) if planes else (None, None)
     out32 = None if planes else torch.empty((b, c_out, oh, ow), dtype=torch.float32, device=dev)
@@ -306,18 +301,18 @@ def _conv(conv: nn.Conv2d, x: O.BF, b: int, h: int, w: int, split: bool, planes:
         c1 = min(c_out, c0 + 512)
 
         def pack():
-            n = L.lvq_conv2d_packed_elems(F.cint(c1 - c0), F.cint(c_in), F.cint(k), F.cint(0))
+            n = L.lvq_conv2d_packed_elems(c1 - c0, c_in, k, 0)
             if n == 0:
                 raise F.LvqError(f"lvq_conv2d: Conv2d({c_in} -> {c1 - c0}) is outside the kernel family")
             wt = conv.weight.detach().float()[c0:c1].contiguous()
             hi, lo = O._bf_empty((n,), dev, split)
-            F.check(L.lvq_conv2d_pack_weights(F.ptr(wt), F.cint(c1 - c0), F.cint(c_in), F.cint(k), F.cint(0), F.ptr(hi), F.ptr(lo), F.stream_ptr(dev)),
+            F.check(L.lvq_conv2d_pack_weights(F.ptr(wt), c1 - c0, c_in, k, 0, F.ptr(hi), F.ptr(lo), F.stream_ptr(dev)),
                     "lvq_conv2d_pack_weights")
             return hi, lo
         wh, wl = _cached(conv, ("conv", c0, c1, split), (conv.weight,), pack)
-        F.check(L.lvq_conv2d(F.ptr(x[0]), F.ptr(x[1]), F.cint(b), F.cint(h), F.cint(w), F.cint(c_in), F.ptr(wh), F.ptr(wl), F.cint(c1 - c0),
-                             F.cint(k), F.cint(s), F.ptr(None), F.ptr(None), F.cint(0), F.ptr(out_bf[0]), F.ptr(out_bf[1]), F.ptr(out32),
-                             F.cint(c_out), F.cint(c0), F.stream_ptr(dev)), "lvq_conv2d")
+        F.check(L.lvq_conv2d(F.ptr(x[0]), F.ptr(x[1]), b, h, w, c_in, F.ptr(wh), F.ptr(wl), c1 - c0,
+                             k, s, F.ptr(None), F.ptr(None), 0, F.ptr(out_bf[0]), F.ptr(out_bf[1]), F.ptr(out32),
+                             c_out, c0, F.stream_ptr(dev)), "lvq_conv2d")
     return (out_bf if planes else out32), oh, ow
 
 

@@ -46,6 +46,54 @@ def test_host_only_entry_points(lib):
     assert lib.lvq_voxelize_dynamic_workspace_bytes(ctypes.c_int64(10), ctypes.c_int(64), g2, ctypes.c_int(3)) == 0
 
 
+@pytest.fixture
+def fresh(lib, monkeypatch):
+    """A handle loaded anew by _ffi.lib(): nothing but the loader has touched its function objects."""
+    monkeypatch.setattr(_ffi, "_lib", None)
+    return _ffi.lib()
+
+
+def test_every_entry_point_is_bound_from_the_header(fresh):
+    """Every declared function carries the argtypes and the restype of its declaration in include/lvq.h."""
+    import re
+    protos = _ffi.prototypes()
+    names = _ffi.declared_symbols()
+    assert sorted(protos) == names and len(names) >= 90
+    with open(_ffi.HEADER_PATH) as f:
+        header = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    size_t_decls = [n for n in names if f"size_t {n}(" in header]
+    assert len(size_t_decls) == 24
+    for name in names:
+        fn = getattr(fresh, name)
+        params = header.split(name + "(", 1)[1].split(")", 1)[0].strip()
+        assert fn.argtypes is not None and len(fn.argtypes) == (0 if params == "void" else params.count(",") + 1), name
+        want = (ctypes.c_size_t if name in size_t_decls else ctypes.c_char_p if name in ("lvq_strerror", "lvq_version")
+                else None if name == "lvq_tuning_defaults" else ctypes.c_int)
+        assert fn.restype is want, name
+
+
+def test_size_results_are_64_bit_without_a_patch(fresh):
+    assert fresh.lvq_stream_guard_workspace_bytes(65536, 65536) == 65536 * 65536 * 4 + 256
+
+
+def test_bare_python_ints_reach_int64_parameters_whole(fresh):
+    big = fresh.lvq_voxelize_hard_workspace_bytes(2**31 + 32768, 1)
+    assert big > fresh.lvq_voxelize_hard_workspace_bytes(32768, 1)
+    assert big == fresh.lvq_voxelize_hard_workspace_bytes(_ffi.i64(2**31 + 32768), _ffi.cint(1))
+
+
+def test_wrong_width_is_an_error(fresh):
+    with pytest.raises(ctypes.ArgumentError):
+        fresh.lvq_colsum_workspace_bytes(_ffi.cint(5), _ffi.cint(8))
+    assert fresh.lvq_strerror(0) == b"ok"
+
+
+def test_prototypes_refuse_unknown_types():
+    with pytest.raises(_ffi.LvqError):
+        _ffi.prototypes("int lvq_x(double a);")
+    assert _ffi.prototypes("int lvq_x(const float *const *p, lvq_stream_t s);") == {"lvq_x": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p])}
+
+
 def test_tuning_record_is_the_only_routing_input(lib, monkeypatch):
     """Kernel-family choices enter through lvq_set_tuning (include/lvq.h: lvq_tuning), not through the environment: the library does not
     import getenv at all, the record round-trips through the ABI, and the Python mirror maps the LVQ_* variables onto it."""

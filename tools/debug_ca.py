@@ -4,7 +4,7 @@ import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np, torch
-from lidar_vision_vqa_amd import fusion, synth, ops
+from lidar_vision_vqa_amd import _ffi as F, fusion, synth, ops
 
 dev = torch.device("cuda:0")
 torch.set_grad_enabled(False)
@@ -44,7 +44,7 @@ B, nq, nkv = 1, 128, 196
 q, kv = synth.randn((B, nq, d), 502), synth.randn((B, nkv, d), 503)
 out = blk.cross_attention(torch.from_numpy(q).to(dev), torch.from_numpy(kv).to(dev))
 torch.cuda.synchronize()
-ws = ops._ATT_WS[(0, "ca_fused")].cpu().numpy()
+ws = F._WORKSPACES[(0, "ca_fused", None)].cpu().numpy()
 KC, CF = 7, 64
 fr = ws[:B * h * CF * 1024].view(np.float16).reshape(B, h, CF, 64, 8).astype(np.float64)
 K = kv[0].astype(np.float64) @ W[d:2 * d].T + sd["ca.in_proj_bias"][d:2 * d]
