@@ -214,12 +214,14 @@ int lvq_layernorm(const float *x, const float *add, int add_rows, int add_group,
  * out_proj; vat_blocks.py:28-34, vat_lidar.py:88,93-97,117-120, vat_vision.py:118-137,
  * build_linear.py:18-19), batched over `batch` problems with element strides a_bs / w_bs / c_bs:
  *   C[z][m, n] = epi( sum_k A[z][m,k] * W[z][n,k] )     A rows lda apart, W rows ldw apart, C rows ldc apart
- *   epi(x): x += bias[n]; GELU(x) (exact erf) if flags & LVQ_GEMM_GELU; x *= alpha;
+ *   epi(x): x += bias[n]; GELU(x) (exact erf) if flags & LVQ_GEMM_GELU, or x / (1 + exp(-1.702 x)) in fp32 if flags &
+ *           LVQ_GEMM_QUICK_GELU (quick_gelu, clip_sdpa.py:73-74,182; -0 or a tiny negative value for large negative x, never NaN;
+ *           both flags together: LVQ_EINVAL); x *= alpha;
  *           x += residual[z][m,n] (fp32, same layout as C) ; x += rowtab[(m % rowtab_rows), n] (fp32 [rows,N]:
  *           input-independent positional tables, geo_pe + view_embed[sid] of vat_lidar.py:235-248)
  *   outputs: c_f32 and/or c_bf16 (+ c_lo).  a_lo / w_lo both NULL (bf16) or both non-NULL (bf16x3).
  *   Requirements: k, lda, ldw, a_bs, w_bs multiples of 8; 16-byte aligned operand bases (else LVQ_EUNSUPPORTED). */
-enum { LVQ_GEMM_GELU = 1 };
+enum { LVQ_GEMM_GELU = 1, LVQ_GEMM_QUICK_GELU = 2 };
 int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_bf16 *w, const lvq_bf16 *w_lo,
                   const float *bias, const float *residual, const float *rowtab, int64_t rowtab_rows,
                   float alpha, int flags, int64_t m, int n, int k, int64_t lda, int64_t ldw, int64_t ldc,
@@ -401,6 +403,25 @@ int lvq_attention_relpos_bf16(const lvq_bf16 *qkv, const lvq_bf16 *qkv_lo, int64
                               const lvq_bf16 *rel_h_lo, const lvq_bf16 *rel_w, const lvq_bf16 *rel_w_lo, int batch, int n_heads,
                               int gh, int gw, int dh, float scale, lvq_bf16 *o, lvq_bf16 *o_lo, int64_t ldo, void *ws,
                               size_t ws_bytes, lvq_stream_t stream);
+
+/* ---- Embedding step of the CLIP-L tower on channel-major patch features (csrc/clip_embed.hip) -----------------------------------
+ * CLIPVisionEmbeddings.forward + VitModel.pre_layrnorm (deepencoder/clip_sdpa.py:147-169, 362-363) in one transposing launch, and
+ * with it the token-major copy of the same features that the projector reads (deepencoder_infer.py: sam_feats.flatten(2).permute):
+ *   feat    [batch, c, hw] fp32   channel-major patch features (SAM's output, or the tower's own patch conv's)
+ *   cls     [c] fp32              class_embedding
+ *   pos     [1 + hw, c] fp32      position table ALREADY at this grid (get_abs_pos is input-independent: the caller resamples it)
+ *   gamma, beta [c] (beta may be NULL), eps      pre_layrnorm
+ *   hidden  [batch * (1 + hw), c] fp32 = LayerNorm(cat(cls, feat^T) + pos): row b (1 + hw) is the class row of image b
+ *   tok_hi, tok_lo (optional)  [batch * hw, ld_tok] bf16 = feat^T as a GEMM operand, exactly lvq_cast_bf16 of the transposed array
+ *           (hi, and lo = x - hi when tok_lo is given); columns c .. ld_tok - 1 are not written
+ * Statistics are fp32 and centred (mean first, then the sum of squared differences), as in lvq_layernorm.
+ * Family: c % 64 == 0, c <= 2048, hw >= 1, batch >= 1 (lvq_clip_embed_ok is that rule); otherwise LVQ_EUNSUPPORTED.  16-byte aligned
+ * feat / cls / pos / gamma / beta / hidden, 4-byte aligned tok_hi / tok_lo, ld_tok even and >= c, batch * (1 + hw) < 2^31 (else
+ * LVQ_EUNSUPPORTED); tok_lo without tok_hi: LVQ_EINVAL.  No workspace.  Every refusal happens before any launch, outputs untouched. */
+int lvq_clip_embed_ok(int batch, int c, int hw);
+int lvq_clip_embed(const float *feat, const float *cls, const float *pos, const float *gamma, const float *beta, float eps,
+                   int batch, int c, int hw, float *hidden, lvq_bf16 *tok_hi, lvq_bf16 *tok_lo, int64_t ld_tok,
+                   lvq_stream_t stream);
 
 /* ---- Fused short-K/V cross-attention sub-path (csrc/cross_fused.hip) -------------------------------------------------------
  * out = q + ca(ca_ln(q), kv, kv): encoder-decoder/training/models/vat_blocks.py:41-42 (nn.LayerNorm + nn.MultiheadAttention with

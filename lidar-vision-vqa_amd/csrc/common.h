@@ -87,6 +87,9 @@ __device__ __forceinline__ uint16_t f32_to_bf16(float f) {
 }
 
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+// QuickGELU x sigmoid(1.702 x) (clip_sdpa.py:73-74) as ONE divide: for large negative x the exponential overflows to +inf and
+// x / inf = -0; the product form x * (1 / (1 + inf)) gives the same, but exp(+1.702 x) / (1 + exp(+1.702 x)) would be inf / inf
+__device__ __forceinline__ float gelu_quick(float x) { return x / (1.0f + expf(-1.702f * x)); }
 
 // rotary frequency of pair e of a dh-wide head as transformers' Qwen2 rotary embedding computes it in fp32:
 // inv_freq = 1 / theta ** (arange(0, dh, 2) / dh), the power rounded once (evaluated in fp64).  powf(theta, -2e/dh) differs from it

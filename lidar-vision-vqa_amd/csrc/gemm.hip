@@ -295,7 +295,8 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_bf16(GemmArgs g) {
 
     // ---- epilogue ----
     // C/D layout of 16x16x32: lane l holds rows (l>>4)*4 + r, column l & 15 of each 16x16 tile.
-    constexpr bool gelu = GELU != 0;     // template parameter: the inlined erff() is only instantiated where it is used
+    constexpr bool gelu = GELU == 1;     // template parameter: the inlined erff() is only instantiated where it is used
+    constexpr bool qgelu = GELU == 2;    // LVQ_GEMM_QUICK_GELU: x sigmoid(1.702 x), a third value of the same parameter
     if (g.vec_epilogue) {
         // Transpose through a wave-private LDS slab so that every lane owns 8 CONSECUTIVE columns of one row:
         // bias / residual / table reads and all stores become 16- or 32-byte accesses (the direct layout
@@ -333,6 +334,10 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_bf16(GemmArgs g) {
                     if (gelu) {
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
+                    }
+                    if (qgelu) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) v[e] = gelu_quick(v[e]);
                     }
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] *= g.alpha;
@@ -395,6 +400,7 @@ __global__ void __launch_bounds__(NW * 64) k_gemm_bf16(GemmArgs g) {
                 if (row >= g.M) continue;
                 float v = acc[i][j][r] + bias;
                 if (gelu) v = gelu_erf(v);
+                if (qgelu) v = gelu_quick(v);
                 v *= g.alpha;
                 const int64_t o = z * g.c_bs + row * g.ldc + col;
                 if (g.residual) v += g.residual[o];
@@ -437,9 +443,13 @@ __device__ __forceinline__ void store_chunk8(const GemmArgs &g, int64_t z, int64
         const float4 b0 = *reinterpret_cast<const float4 *>(g.bias + col), b1 = *reinterpret_cast<const float4 *>(g.bias + col + 4);
         v[0] += b0.x; v[1] += b0.y; v[2] += b0.z; v[3] += b0.w; v[4] += b1.x; v[5] += b1.y; v[6] += b1.z; v[7] += b1.w;
     }
-    if (GELU) {
+    if (GELU == 1) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
+    }
+    if (GELU == 2) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = gelu_quick(v[e]);
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] *= g.alpha;
@@ -1054,7 +1064,9 @@ __device__ __forceinline__ void bf8_to_f32(const uint4 v, float (&f)[8]) {
 // NORM: A is not read as bf16 but produced on the fly as RMSNorm(xf) * gamma rounded to bf16 (hi[, lo]) -- exactly what lvq_rmsnorm
 // writes (same per-lane summation order, same expression), so the result is bit-identical to the rmsnorm + GEMV pair while two of
 // the ~12 launches of a decoder layer disappear (a one-row norm kernel costs 12.8 us of dependent latency, 0.63 ms per token).
-template <int MM, bool X3, int GEMV_R, int PRO>
+// QG: the activation is QuickGELU (LVQ_GEMM_QUICK_GELU) and `gelu` is not read; QG = false is the kernel as it always was, with its
+// run-time exact-erf switch
+template <int MM, bool X3, int GEMV_R, int PRO, bool QG = false>
 __global__ void __launch_bounds__(256) k_gemv(const uint16_t *__restrict__ a, const uint16_t *__restrict__ a_lo, const uint16_t *__restrict__ w,
                                               const uint16_t *__restrict__ w_lo, const float *__restrict__ bias, const float *__restrict__ residual,
                                               const float *__restrict__ rowtab, int64_t rowtab_rows, float alpha, int gelu, int m, int n, int k,
@@ -1146,7 +1158,8 @@ __global__ void __launch_bounds__(256) k_gemv(const uint16_t *__restrict__ a, co
                 for (int b_ = 0; b_ < GEMV_R; ++b_)
                     if (a_ == mi && b_ == r) x = acc[a_][b_];
             if (bias) x += bias[col];
-            if (gelu) x = gelu_erf(x);
+            if (QG) x = gelu_quick(x);
+            else if (gelu) x = gelu_erf(x);
             x *= alpha;
             const int64_t o = (int64_t)mi * ldc + col;
             if (residual) x += residual[o];
@@ -1161,12 +1174,23 @@ __global__ void __launch_bounds__(256) k_gemv(const uint16_t *__restrict__ a, co
     }
 }
 
+
+// gelu: 0 none, 1 exact erf, 2 QuickGELU (k_gemv<.., QG = true>; the RMSNorm prologue form has no caller that asks for it)
 template <int MM, int R, int PRO>
 static void launch_gemv_r(bool x3, hipStream_t st, const uint16_t *a, const uint16_t *a_lo, const uint16_t *w, const uint16_t *w_lo,
                           const float *bias, const float *residual, const float *rowtab, int64_t rowtab_rows, float alpha, int gelu, int m, int n,
                           int k, int64_t lda, int64_t ldw, int64_t ldc, float *c32, uint16_t *c16, uint16_t *c16lo, const float *xf,
                           const float *gamma, float eps) {
     const dim3 grid((unsigned)lvq_cdiv(n, 4 * R));
+    if constexpr (PRO == 0) {
+        if (gelu == 2) {
+            if (x3) hipLaunchKernelGGL((k_gemv<MM, true, R, 0, true>), grid, dim3(256), 0, st, a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha,
+                                       gelu, m, n, k, lda, ldw, ldc, c32, c16, c16lo, xf, gamma, eps);
+            else hipLaunchKernelGGL((k_gemv<MM, false, R, 0, true>), grid, dim3(256), 0, st, a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha,
+                                    gelu, m, n, k, lda, ldw, ldc, c32, c16, c16lo, xf, gamma, eps);
+            return;
+        }
+    }
     if (x3) hipLaunchKernelGGL((k_gemv<MM, true, R, PRO>), grid, dim3(256), 0, st, a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha, gelu, m,
                                n, k, lda, ldw, ldc, c32, c16, c16lo, xf, gamma, eps);
     else hipLaunchKernelGGL((k_gemv<MM, false, R, PRO>), grid, dim3(256), 0, st, a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha, gelu, m,
@@ -1212,13 +1236,16 @@ extern "C" int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_
     if (a_lo != nullptr && w_lo == nullptr) return LVQ_EINVAL;
     if (c_lo && !c_bf16) return LVQ_EINVAL;
     if (rowtab && rowtab_rows <= 0) return LVQ_EINVAL;
+    if ((flags & LVQ_GEMM_GELU) && (flags & LVQ_GEMM_QUICK_GELU)) return LVQ_EINVAL;      // one activation per call
     if (m == 0) return LVQ_OK;
+    // activation of the epilogue = the kernels' GELU template value: 0 none, 1 exact erf, 2 QuickGELU
+    const int act = (flags & LVQ_GEMM_QUICK_GELU) ? 2 : (flags & LVQ_GEMM_GELU) ? 1 : 0;
     // 16-byte operand loads: K, leading dims and batch strides in multiples of 8 elements, 16-B aligned bases
     if ((k & 7) || (lda & 7) || (ldw & 7) || (a_bs & 7) || (w_bs & 7) || lda < k || ldw < k || ldc < n)
         return LVQ_EUNSUPPORTED;
     if (((uintptr_t)a | (uintptr_t)w | (uintptr_t)a_lo | (uintptr_t)w_lo) & 15) return LVQ_EUNSUPPORTED;
     if (m <= 8 && batch == 1 && n >= 64 && (a_lo != nullptr || w_lo == nullptr) && !lvq_tune().gemm_no_gemv) {   // skinny M: stream W once (k_gemv)
-        launch_gemv<0>(a_lo != nullptr, lvq_s(stream), a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha, (flags & LVQ_GEMM_GELU) != 0,
+        launch_gemv<0>(a_lo != nullptr, lvq_s(stream), a, a_lo, w, w_lo, bias, residual, rowtab, rowtab_rows, alpha, act,
                            (int)m, n, k, lda, ldw, ldc, c_f32, c_bf16, c_lo, nullptr, nullptr, 0.f);
         return lvq_launch_status();
     }
@@ -1247,7 +1274,6 @@ extern "C" int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_
     hipStream_t st = lvq_s(stream);
     const int64_t big_tiles = lvq_cdiv(m, 128) * lvq_cdiv(n, 128) * batch;
     const bool dma = (k % 64) == 0;      // LDS-DMA path needs whole 64-wide K tiles (no per-chunk zero fill)
-    const bool ge = (flags & LVQ_GEMM_GELU) != 0;
     // 256x128 / 8 waves / 3 stages when there is enough work to fill the chip with the bigger tile
     const bool huge = dma && lvq_cdiv(m, 256) * lvq_cdiv(n, 128) * batch >= 512 && !lvq_tune().gemm_no256;
     if (batch > 65535) return LVQ_EUNSUPPORTED;
@@ -1263,11 +1289,12 @@ extern "C" int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_
         (m / 256) * (n / 256) <= 0x7fffffff && !lvq_tune().gemm_no256x256 && !lvq_tune().gemm_no256) {
         const size_t lds = (size_t)5 * 256 * 128;              // A ring 3 x 32 KiB + W ring 2 x 32 KiB
         if (lvq_ensure_lds(once256, {(const void *)k_gemm_256<0, 0>, (const void *)k_gemm_256<1, 0>, (const void *)k_gemm_256<0, 1>,
-                                     (const void *)k_gemm_256<1, 1>}, lds)) {
+                                     (const void *)k_gemm_256<1, 1>, (const void *)k_gemm_256<2, 0>, (const void *)k_gemm_256<2, 1>}, lds)) {
             g.ntx = (int)(n / 256);
             dim3 grid((unsigned)((m / 256) * (n / 256)), 1, (unsigned)batch);
             const bool ant = g.ntx <= 8;
-            if (ge) { if (ant) hipLaunchKernelGGL((k_gemm_256<1, 1>), grid, dim3(512), lds, st, g); else hipLaunchKernelGGL((k_gemm_256<1, 0>), grid, dim3(512), lds, st, g); }
+            if (act == 2)      { if (ant) hipLaunchKernelGGL((k_gemm_256<2, 1>), grid, dim3(512), lds, st, g); else hipLaunchKernelGGL((k_gemm_256<2, 0>), grid, dim3(512), lds, st, g); }
+            else if (act == 1) { if (ant) hipLaunchKernelGGL((k_gemm_256<1, 1>), grid, dim3(512), lds, st, g); else hipLaunchKernelGGL((k_gemm_256<1, 0>), grid, dim3(512), lds, st, g); }
             else    { if (ant) hipLaunchKernelGGL((k_gemm_256<0, 1>), grid, dim3(512), lds, st, g); else hipLaunchKernelGGL((k_gemm_256<0, 0>), grid, dim3(512), lds, st, g); }
             return lvq_launch_status();
         }
@@ -1278,9 +1305,11 @@ extern "C" int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_
         g.ntx = (int)lvq_cdiv(n, 128);
         const size_t lds = (size_t)3 * (256 + 128) * 128;
         static LvqLdsOnce once;
-        if (!lvq_ensure_lds(once, {(const void *)k_gemm_bf16<256, 128, 1, 0, 8>, (const void *)k_gemm_bf16<256, 128, 1, 1, 8>}, lds)) return LVQ_ELAUNCH;
+        if (!lvq_ensure_lds(once, {(const void *)k_gemm_bf16<256, 128, 1, 0, 8>, (const void *)k_gemm_bf16<256, 128, 1, 1, 8>,
+                                   (const void *)k_gemm_bf16<256, 128, 1, 2, 8>}, lds)) return LVQ_ELAUNCH;
         dim3 grid((unsigned)tiles, 1, (unsigned)batch);
-        if (ge) hipLaunchKernelGGL((k_gemm_bf16<256, 128, 1, 1, 8>), grid, dim3(512), lds, st, g);
+        if (act == 2)      hipLaunchKernelGGL((k_gemm_bf16<256, 128, 1, 2, 8>), grid, dim3(512), lds, st, g);
+        else if (act == 1) hipLaunchKernelGGL((k_gemm_bf16<256, 128, 1, 1, 8>), grid, dim3(512), lds, st, g);
         else    hipLaunchKernelGGL((k_gemm_bf16<256, 128, 1, 0, 8>), grid, dim3(512), lds, st, g);
         return lvq_launch_status();
     }
@@ -1291,13 +1320,13 @@ extern "C" int lvq_gemm_bf16(const lvq_bf16 *a, const lvq_bf16 *a_lo, const lvq_
     dim3 grid((unsigned)tiles, 1, (unsigned)batch);
     const size_t lds = (size_t)((bm == 64 && dma) ? 3 : 2) * (bm + bm) * 128;
 #define LVQ_LAUNCH(BM_, DMA_, GE_) hipLaunchKernelGGL((k_gemm_bf16<BM_, BM_, DMA_, GE_, 4>), grid, dim3(256), lds, st, g)
+#define LVQ_LAUNCH_ACT(BM_, DMA_) do { if (act == 2) LVQ_LAUNCH(BM_, DMA_, 2); else if (act == 1) LVQ_LAUNCH(BM_, DMA_, 1); else LVQ_LAUNCH(BM_, DMA_, 0); } while (0)
     if (bm == 128) {
-        if (dma) { if (ge) LVQ_LAUNCH(128, 1, 1); else LVQ_LAUNCH(128, 1, 0); }
-        else     { if (ge) LVQ_LAUNCH(128, 0, 1); else LVQ_LAUNCH(128, 0, 0); }
+        if (dma) LVQ_LAUNCH_ACT(128, 1); else LVQ_LAUNCH_ACT(128, 0);
     } else {
-        if (dma) { if (ge) LVQ_LAUNCH(64, 1, 1); else LVQ_LAUNCH(64, 1, 0); }
-        else     { if (ge) LVQ_LAUNCH(64, 0, 1); else LVQ_LAUNCH(64, 0, 0); }
+        if (dma) LVQ_LAUNCH_ACT(64, 1); else LVQ_LAUNCH_ACT(64, 0);
     }
+#undef LVQ_LAUNCH_ACT
 #undef LVQ_LAUNCH
     return lvq_launch_status();
 }

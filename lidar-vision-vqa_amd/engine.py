@@ -16,8 +16,9 @@ Two deliberate differences from the reference:
   * it decodes `outputs[0][inputs_embeds.shape[1]:]`, but an inputs_embeds-only `generate` returns ONLY the new tokens, so that
     slice is empty whenever max_new_tokens < prompt length and the reference answers "" (recorded in tests/golden/engine.npz).
     The new tokens are what is decoded here.
-  * `process_vision` needs the SAM / CLIP DeepEncoder towers (weights fetched by URL: out of scope); the six
-    per-view token tensors come from `models["multiview_tokens_fn"](sample_token)` instead of `runtime` / `nusc`.
+  * `process_vision` takes the six per-view token tensors from `models["multiview_tokens_fn"](sample_token)` when that is given;
+    otherwise `models["runtime"]` (deepencoder.DeepEncoderRuntime) encodes the six camera files named by
+    `models["view_paths_fn"](sample_token)`, or by `resolve_cam_image_paths(nusc, sample_token)`.  Weights are never fetched by URL.
 """
 from __future__ import annotations
 
@@ -107,7 +108,7 @@ class InferenceEngine:
         self.tokenizer, self.base_model, self.vat_lidar = models["tokenizer"], models["base_model"], models["vat_lidar"]
         self.vat_vision, self.vision_adapter = models.get("vat_vision"), models.get("vision_adapter")
         self.runtime, self.nusc = models.get("runtime"), models.get("nusc")
-        self.multiview_tokens_fn = models.get("multiview_tokens_fn")
+        self.multiview_tokens_fn, self.view_paths_fn = models.get("multiview_tokens_fn"), models.get("view_paths_fn")
         self.config, self.device, self.d_model = models["config"], models["device"], models["d_model"]
         self.use_vision = bool(self.config.get("use_vision", False)) and self.vat_vision is not None
         self.prefix_scale = self.config.get("prefix_scale", 0.2)
@@ -134,6 +135,11 @@ class InferenceEngine:
         (inference_engine.py:104-137)."""
         if not self.use_vision:
             return None
+        if self.multiview_tokens_fn is None and self.runtime is not None:
+            from .deepencoder import resolve_cam_image_paths
+            paths = self.view_paths_fn(sample_token) if self.view_paths_fn is not None else resolve_cam_image_paths(self.nusc, sample_token)
+            views = [t.to(self.device) for t in self.runtime.encode_views(paths, strict=False)["tokens"]]
+            return self.vat_vision(self.vision_adapter(views)[None])
         if self.multiview_tokens_fn is None:
             raise F.LvqError("process_vision: pass models['multiview_tokens_fn'](sample_token) -> six [HW, d_in] tensors; the "
                              "DeepEncoder towers are outside this build (DESIGN section 6)")

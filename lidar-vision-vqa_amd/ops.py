@@ -109,31 +109,67 @@ def rmsnorm(x: torch.Tensor, gamma: torch.Tensor, eps: float, split: bool) -> BF
     return hi, lo
 
 
-def linear(a: BF, w: BF, bias: Optional[torch.Tensor] = None, *, gelu: bool = False, alpha: float = 1.0,
+GEMM_GELU, GEMM_QUICK_GELU = 1, 2          # include/lvq.h: LVQ_GEMM_GELU, LVQ_GEMM_QUICK_GELU
+
+
+def linear(a: BF, w: BF, bias: Optional[torch.Tensor] = None, *, gelu: bool = False, quick_gelu: bool = False, alpha: float = 1.0,
            residual: Optional[torch.Tensor] = None, rowtab: Optional[torch.Tensor] = None, out_f32: bool = False,
-           out_bf: bool = False, w_rows: Optional[Tuple[int, int]] = None, tag: Optional[str] = None):
-    """y = a @ w[r0:r1].T (+bias[r0:r1]) ... ; a hi [M,K], w hi [N,K].  Returns (y_f32 | None, BF | None)."""
+           out_bf: bool = False, w_rows: Optional[Tuple[int, int]] = None, w_cols: Optional[Tuple[int, int]] = None,
+           a_rows: Optional[Tuple[int, int, int, int]] = None, tag: Optional[str] = None):
+    """y = a @ w[r0:r1, c0:c1].T (+bias[r0:r1]) ... ; a hi [M, K], w hi [N, Kw] with K = c1 - c0 (the column slice is read through
+    ldw = Kw, no copy).  a_rows = (batch, stride, first, m): rows first .. first + m - 1 of every `stride` rows of a, `batch` times
+    (one batched launch; the rows between are skipped by the batch stride) -> y [batch * m, N].  gelu / quick_gelu: the epilogue's
+    activation (exact erf / x sigmoid(1.702 x)).  Returns (y_f32 | None, BF | None)."""
     ah, al = a
     wh, wl = w
-    m, k = ah.shape
+    kw = wh.shape[1]
     r0, r1 = w_rows if w_rows is not None else (0, wh.shape[0])
-    n = r1 - r0
-    assert wh.shape[1] == k and (al is None or wl is not None)      # plain | bf16x3 | a plain, w split ("x2w")
+    c0, c1 = w_cols if w_cols is not None else (0, kw)
+    n, k = r1 - r0, c1 - c0
+    batch, a_bs, first, m = (1, 0, 0, ah.shape[0]) if a_rows is None else (a_rows[0], a_rows[1] * k, a_rows[2], a_rows[3])
+    assert ah.shape[1] == k and (al is None or wl is not None)      # plain | bf16x3 | a plain, w split ("x2w")
+    assert (first + m) + (batch - 1) * (a_bs // k) <= ah.shape[0] and c0 % 8 == 0
     dev = ah.device
     split = wl is not None
-    c32 = torch.empty((m, n), dtype=torch.float32, device=dev) if out_f32 else None
-    ch, cl = _bf_empty((m, n), dev, al is not None) if out_bf else (None, None)
-    wo = r0 * k * 2  # byte offset of the weight row slice
+    rows = batch * m
+    c32 = torch.empty((rows, n), dtype=torch.float32, device=dev) if out_f32 else None
+    ch, cl = _bf_empty((rows, n), dev, al is not None) if out_bf else (None, None)
+    wo = (r0 * kw + c0) * 2  # byte offset of the weight slice
+    ao = first * k * 2
     bo = r0 * 4
     with region(tag, dev):
         rc = F.lib().lvq_gemm_bf16(
-            F.ptr(ah), F.ptr(al), wh.data_ptr() + wo, wl.data_ptr() + wo if split else None,
+            ah.data_ptr() + ao, al.data_ptr() + ao if al is not None else None, wh.data_ptr() + wo, wl.data_ptr() + wo if split else None,
             bias.data_ptr() + bo if bias is not None else None, F.ptr(residual), F.ptr(rowtab),
-            rowtab.shape[0] if rowtab is not None else 0, alpha, 1 if gelu else 0, m, n,
-            k, k, k, n, 1, 0, 0, 0, F.ptr(c32), F.ptr(ch), F.ptr(cl),
+            rowtab.shape[0] if rowtab is not None else 0, alpha, (GEMM_GELU if gelu else 0) | (GEMM_QUICK_GELU if quick_gelu else 0), m, n,
+            k, k, kw, n, batch, a_bs, 0, 0 if a_rows is None else m * n, F.ptr(c32), F.ptr(ch), F.ptr(cl),
             F.stream_ptr(dev))
-    F.check(rc, f"lvq_gemm_bf16 (m={m}, n={n}, k={k})")
+    F.check(rc, f"lvq_gemm_bf16 (m={m}, n={n}, k={k}, batch={batch})")
     return c32, ((ch, cl) if out_bf else None)
+
+
+def clip_embed_ok(batch: int, c: int, hw: int) -> bool:
+    """lvq_clip_embed_ok: the embedding kernel takes (batch, c, hw)."""
+    return bool(F.lib().lvq_clip_embed_ok(batch, c, hw))
+
+
+def clip_embed(feat: torch.Tensor, cls: torch.Tensor, pos: torch.Tensor, gamma: torch.Tensor, beta: Optional[torch.Tensor], eps: float,
+               *, want_tok: bool = False, split: bool = False, tag: Optional[str] = None):
+    """lvq_clip_embed.  feat [B, c, hw] fp32 channel-major, cls [c], pos [1 + hw, c] -> (hidden [B * (1 + hw), c] fp32,
+    tok BF [B * hw, c] | None): LayerNorm(cat(cls, feat^T) + pos), and feat^T as a GEMM operand (hi, lo with `split`)."""
+    F.require_cuda(feat, cls, pos, gamma, beta)
+    if feat.dim() != 3 or feat.dtype != torch.float32:
+        raise F.LvqError(f"clip_embed: feat must be fp32 [batch, c, hw], got {feat.dtype} {tuple(feat.shape)}")
+    b, c, hw = feat.shape
+    if tuple(cls.shape) != (c,) or tuple(pos.shape) != (1 + hw, c) or tuple(gamma.shape) != (c,):
+        raise F.LvqError(f"clip_embed: cls {tuple(cls.shape)}, pos {tuple(pos.shape)}, gamma {tuple(gamma.shape)} do not fit feat {tuple(feat.shape)}")
+    hidden = torch.empty((b * (1 + hw), c), dtype=torch.float32, device=feat.device)
+    th, tl = _bf_empty((b * hw, c), feat.device, split) if want_tok else (None, None)
+    with region(tag, feat.device):
+        rc = F.lib().lvq_clip_embed(F.ptr(feat), F.ptr(cls), F.ptr(pos), F.ptr(gamma), F.ptr(beta), eps, b, c, hw, F.ptr(hidden),
+                                    F.ptr(th), F.ptr(tl), c, F.stream_ptr(feat.device))
+    F.check(rc, f"lvq_clip_embed (batch={b}, c={c}, hw={hw})")
+    return hidden, ((th, tl) if want_tok else None)
 
 
 def attention(q: BF, k: BF, v: BF, *, batch: int, n_heads: int, n_kv_heads: int, nq: int, nkv: int, dh: int,

@@ -1,0 +1,261 @@
+"""CPU checks of the CLIP tower and the DeepEncoder runtime: the fp64 restatement of tests/clip_tower_cases.py against every golden of
+the unmodified reference (2e-5 max(1, max|ref|), the bar of tests/test_oracle_vat.py), the sensitivity of each of its variants, the
+modules' state-dict contract, the host image preparation, the weight-key mapping, the no-network rule and the CUDA-less error paths."""
+import os
+import re
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import clip_tower_cases as CC
+import vision_tower_cases as VC
+from lidar_vision_vqa_amd import _ffi as F
+from lidar_vision_vqa_amd import clip_tower as CT
+from lidar_vision_vqa_amd import deepencoder as DE
+from lidar_vision_vqa_amd import fusion
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+BAR = 2e-5
+SENSITIVITY = 0.05                                       # 50 x the 1e-3 parity bar
+
+
+def golden(name):
+    return np.load(os.path.join(GOLDEN, CC.golden_name(name)))
+
+
+def rel(a, b):
+    return float(np.abs(a - b).max()) / max(1.0, float(np.abs(b).max()))
+
+
+@pytest.mark.parametrize("name", list(CC.CASES))
+def test_restatement_reproduces_the_reference(name):
+    g = golden(name)
+    ref = CC.case_ref(name)
+    assert list(g["full_shape"]) == list(ref.shape) and list(g["rows"]) == CC.kept_rows(name, ref.shape[1])
+    assert 0 in g["rows"] and ref.shape[1] - 1 in g["rows"]                     # the class row and the last row are among the stored rows
+    err = rel(ref[:, g["rows"]], g["out"])
+    print(f"{name}: restatement vs golden {err:.3e} (max|golden| {np.abs(g['out']).max():.3f})")
+    assert err <= BAR, err
+    assert os.path.getsize(os.path.join(GOLDEN, CC.golden_name(name))) < 1024 * 1024
+
+
+@pytest.mark.parametrize("variant", CC.VARIANTS)
+def test_every_term_is_visible(variant):
+    """Each variant (one term switched off) moves the output of at least one small case by >= 0.05."""
+    moved = {}
+    for name in ("same", "down", "up", "one", "trunc", "zeropad", "own_patch"):
+        moved[name] = rel(CC.case_ref(name, variant), CC.case_ref(name))
+    print(f"{variant}: " + ", ".join(f"{k} {v:.3f}" for k, v in moved.items()))
+    assert max(moved.values()) >= SENSITIVITY, moved
+    if variant == "pos_truncated":                       # only the resampled grids differ from a truncation
+        assert moved["same"] == 0.0 and moved["trunc"] == 0.0 and moved["zeropad"] == 0.0 and min(moved["down"], moved["up"]) >= SENSITIVITY
+
+
+def test_get_abs_pos_four_behaviours():
+    table = torch.from_numpy(CC.case_state("same")["embeddings.position_embedding.weight"])[None]        # [1, 17, 128]
+    assert CT.get_abs_pos(table, 17) is table
+    for tokens in (10, 26, 2, 7, 22):
+        got = CT.get_abs_pos(table, tokens)[0]
+        assert got.shape == (tokens, 128) and got.dtype == torch.float32
+        assert torch.equal(got.double(), CC.abs_pos(table[0].numpy(), tokens))
+    assert torch.equal(CT.get_abs_pos(table, 7)[0], table[0, :7])
+    z = CT.get_abs_pos(table, 22)[0]
+    assert torch.equal(z[:17], table[0]) and not z[17:].any()
+    assert not torch.equal(CT.get_abs_pos(table, 10)[0, 1:], table[0, 1:10])   # resampled, not truncated
+    flat = table[0]
+    assert CT.get_abs_pos(flat, 5) is flat                                      # not [1, N, C]: returned as it is
+
+
+def _keys(m):
+    sd = m.state_dict()
+    return list(sd), [",".join(str(d) for d in v.shape) for v in sd.values()]
+
+
+@pytest.mark.parametrize("name", ["same", "l2_w1024"])
+def test_state_dict_contract(name):
+    g = golden(name)
+    with torch.device("meta"):
+        m = CT.VitModel(CT._Cfg(CC.CASES[name][0]))
+    keys, shapes = _keys(m)
+    assert keys == list(g["keys"]) and shapes == list(g["shapes"])
+    assert keys == [k for k, _ in CC.state_shapes(CC.CASES[name][0])]
+    assert "embeddings.position_ids" not in keys and keys[-2:] == ["pre_layrnorm.weight", "pre_layrnorm.bias"]
+    assert tuple(m.embeddings.position_ids.shape) == (1, m.embeddings.num_positions)
+
+
+def test_build_clip_l_keys_order_and_shapes():
+    with torch.device("meta"):
+        m = CT.build_clip_l()
+    cfg = dict(CC.WIDE, num_layers=24)
+    keys, shapes = _keys(m)
+    want = CC.state_shapes(cfg)
+    assert keys == [k for k, _ in want] and shapes == [",".join(str(d) for d in s) for _, s in want]
+    assert len(m.transformer.layers) == 24 and m.embeddings.num_positions == 257 and str(m) == "open_clip"
+    c = CT.vit_model_cfg
+    assert (c.num_layers, c.hidden_size, c.num_attention_heads, c.ffn_hidden_size, c.image_size, c.patch_size) == (24, 1024, 16, 4096, 224, 14)
+    assert c.get("fp32norm", False) is False and isinstance(c, dict)
+    assert CT.clip_l_lora_default_targets() == ("qkv_proj", "out_proj", "mlp.fc1", "mlp.fc2")
+
+
+def test_default_init_consumes_the_rng_in_the_reference_order():
+    """class_embedding = randn(hidden) first, then the patch conv, the position table, and per block qkv_proj, out_proj, fc1, fc2."""
+    import torch.nn as nn
+    cfg = CT._Cfg(CC.BASE)
+    torch.manual_seed(77)
+    ours = CT.VitModel(cfg)
+    torch.manual_seed(77)
+    cls = torch.randn(128)
+    conv = nn.Conv2d(3, 128, kernel_size=14, stride=14, bias=False)
+    pos = nn.Embedding(17, 128)
+    qkv, out = nn.Linear(128, 384), nn.Linear(128, 128)
+    fc1 = nn.Linear(128, 256)
+    assert torch.equal(ours.embeddings.class_embedding, cls) and torch.equal(ours.embeddings.patch_embedding.weight, conv.weight)
+    assert torch.equal(ours.embeddings.position_embedding.weight, pos.weight)
+    layer = ours.transformer.layers[0]
+    assert torch.equal(layer.self_attn.qkv_proj.weight, qkv.weight) and torch.equal(layer.self_attn.out_proj.bias, out.bias)
+    assert torch.equal(layer.mlp.fc1.weight, fc1.weight)
+
+
+def test_quick_gelu_definition():
+    x = torch.linspace(-6, 6, 101, dtype=torch.float64)
+    assert torch.allclose(CT.quick_gelu(x), CC.quick_gelu(x), rtol=0, atol=1e-15)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------------
+# deepencoder: weight-key mapping, image preparation, no network, error paths
+# ------------------------------------------------------------------------------------------------------------------------------------
+def _openclip_sd(cfg, npos, seed):
+    d, f = cfg["hidden_size"], cfg["ffn_hidden_size"]
+    gen = torch.Generator().manual_seed(seed)
+    r = lambda *s: torch.randn(*s, generator=gen)
+    sd = {"class_embedding": r(d), "positional_embedding": r(1, npos, d), "conv1.weight": r(d, 3, 14, 14)}
+    for i in range(cfg["num_layers"]):
+        p = f"transformer.resblocks.{i}."
+        sd.update({p + "attn.in_proj_weight": r(3 * d, d), p + "attn.in_proj_bias": r(3 * d), p + "attn.out_proj.weight": r(d, d),
+                   p + "attn.out_proj.bias": r(d), p + "mlp.c_fc.weight": r(f, d), p + "mlp.c_fc.bias": r(f), p + "mlp.c_proj.weight": r(d, f),
+                   p + "mlp.c_proj.bias": r(d), p + "ln_1.weight": r(d), p + "ln_1.bias": r(d), p + "ln_2.weight": r(d), p + "ln_2.bias": r(d)})
+    return sd
+
+
+def test_load_openclip_state_dict():
+    cfg = CT._Cfg(CC.BASE)
+    # full match
+    m = CT.VitModel(cfg)
+    conv0 = m.embeddings.patch_embedding.weight.detach().clone()
+    sd = _openclip_sd(CC.BASE, 17, 1)
+    used = DE.load_openclip_state_dict(m, sd)
+    assert len(used) == 2 + 12 * 2 and "conv1.weight" not in used
+    assert torch.equal(m.embeddings.class_embedding, sd["class_embedding"])
+    assert torch.equal(m.embeddings.position_embedding.weight, sd["positional_embedding"][0])
+    assert torch.equal(m.transformer.layers[1].self_attn.qkv_proj.weight, sd["transformer.resblocks.1.attn.in_proj_weight"])
+    assert torch.equal(m.transformer.layers[0].mlp.fc2.bias, sd["transformer.resblocks.0.mlp.c_proj.bias"])
+    assert torch.equal(m.transformer.layers[1].layer_norm2.weight, sd["transformer.resblocks.1.ln_2.weight"])
+    assert torch.equal(m.embeddings.patch_embedding.weight, conv0)              # CLIP's patch conv is not copied
+    # a shorter position table: the first n positions are copied, the rest keep their values
+    m = CT.VitModel(cfg)
+    before = m.embeddings.position_embedding.weight.detach().clone()
+    sd = _openclip_sd(CC.BASE, 10, 2)
+    DE.load_openclip_state_dict(m, sd)
+    assert torch.equal(m.embeddings.position_embedding.weight[:10], sd["positional_embedding"][0])
+    assert torch.equal(m.embeddings.position_embedding.weight[10:], before[10:])
+    # missing keys are skipped
+    m = CT.VitModel(cfg)
+    before = {k: v.detach().clone() for k, v in m.state_dict().items()}
+    sd = _openclip_sd(CC.BASE, 17, 3)
+    for k in ("class_embedding", "transformer.resblocks.0.attn.in_proj_bias", "transformer.resblocks.1.ln_1.weight"):
+        del sd[k]
+    used = DE.load_openclip_state_dict(m, sd)
+    assert len(used) == 1 + 24 - 2
+    assert torch.equal(m.embeddings.class_embedding, before["embeddings.class_embedding"])
+    assert torch.equal(m.transformer.layers[0].self_attn.qkv_proj.bias, before["transformer.layers.0.self_attn.qkv_proj.bias"])
+    assert torch.equal(m.transformer.layers[0].self_attn.qkv_proj.weight, sd["transformer.resblocks.0.attn.in_proj_weight"])
+
+
+def test_image_preparation_matches_the_reference():
+    from PIL import Image
+    g = np.load(os.path.join(GOLDEN, "deepencoder_prep.npz"))
+    assert g["src"].shape == (40, 96, 3)
+    sq = DE.resize_and_pad_to_square(Image.fromarray(g["src"]), target=64)
+    assert sq.size == (64, 64) and np.array_equal(np.array(sq), g["square"])
+    assert not g["square"][:18].any() and g["square"][20:44].any()              # 96 x 40 -> 64 x 27, centred: black bands above and below
+    t = DE._pil_to_tensor_og_norm(sq)
+    assert t.shape == (1, 3, 64, 64) and t.dtype == torch.float32 and np.array_equal(t.numpy(), g["tensor"])
+    assert torch.equal(CC.runtime_pixels(), DE._pil_to_tensor_og_norm(DE.resize_and_pad_to_square(Image.fromarray(CC.runtime_image()))))
+    assert (DE.FIXED_IMAGE_SIZE, DE.FIXED_GRID_SIDE) == (1024, 16)
+    assert DE.DEFAULT_VIEW_ORDER == ("CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_FRONT_LEFT", "CAM_BACK", "CAM_BACK_RIGHT", "CAM_BACK_LEFT")
+
+
+def test_resolve_cam_image_paths_is_duck_typed(tmp_path):
+    (tmp_path / "samples").mkdir()
+    (tmp_path / "samples" / "front.jpg").write_bytes(b"x")
+
+    class Nusc:
+        dataroot = str(tmp_path)
+
+        def get(self, table, token):
+            if table == "sample":
+                return {"data": {"CAM_FRONT": "sd_front", "CAM_BACK": "sd_back"}}
+            return {"filename": {"sd_front": "samples/front.jpg", "sd_back": "samples/back.jpg"}[token]}
+    got = DE.resolve_cam_image_paths(Nusc(), "tok")
+    assert got[0] == (tmp_path / "samples" / "front.jpg").resolve() and got[1:] == [None] * 5
+
+
+def test_the_package_never_reaches_the_network(tmp_path):
+    pkg = os.path.dirname(CT.__file__)
+    for fn in sorted(os.listdir(pkg)):
+        if fn.endswith(".py"):
+            src = open(os.path.join(pkg, fn)).read()
+            assert not re.search(r"^\s*(import|from)\s+(urllib|open_clip|requests|easydict|nuscenes)\b", src, re.M), fn
+            assert not re.search(r"https?://", src), fn
+    with pytest.raises(FileNotFoundError):
+        DE.DeepEncoderRuntime(sam_ckpt=str(tmp_path / "missing.pth"), device="cpu")
+    DE._warned_network = False
+    with warnings.catch_warnings(record=True) as w, torch.device("meta"):
+        warnings.simplefilter("always")
+        rt = DE.DeepEncoderRuntime(sam_ckpt=None, auto_download_sam=True, openclip_pretrained="openai", device="meta")
+        DE.DeepEncoderRuntime(device="meta")
+    assert len([x for x in w if "never" in str(x.message) and "network" in str(x.message)]) == 1
+    assert isinstance(rt.projector, fusion.MlpProjectorLinear) and rt.projector.layers.weight.shape == (2048, 2048)
+    assert len(rt.clip_vit.transformer.layers) == 24 and len(rt.sam.blocks) == 12
+    assert rt.grid == (16, 16) and rt.image_size == 1024 and rt.dtype == torch.bfloat16
+    assert not rt.sam.training and not rt.clip_vit.training and not rt.projector.training
+
+
+def test_inference_only_and_cuda_less_error_paths(tmp_path):
+    with torch.device("meta"):
+        rt = DE.DeepEncoderRuntime(device="meta")
+    with pytest.raises(F.LvqError):
+        rt.train()
+    with pytest.raises(F.LvqError):
+        rt.trainable_parameters()
+    with pytest.raises(F.LvqError), torch.device("meta"):
+        DE.DeepEncoderRuntime(device="meta", lora_config=type("L", (), {"enabled": True})())
+    with pytest.raises(FileNotFoundError):
+        rt.encode_views([tmp_path / "a.png"] * 6, strict=True)
+    with pytest.raises(RuntimeError):
+        rt.encode_views([None] * 6, strict=False)
+    m = CT.VitModel(CT._Cfg(CC.BASE)).eval()
+    x, pe = (torch.from_numpy(a) for a in CC.case_inputs("same"))
+    with pytest.raises(F.LvqError), torch.no_grad():
+        m(x, pe)                                                                # CPU tensors: no fallback
+    with pytest.raises(F.LvqError):
+        m(x, pe)                                                                # gradients in reach
+    with pytest.raises(F.LvqError), torch.no_grad():
+        m.train()(x, pe)
+    with pytest.raises(ValueError):
+        m.eval()(patch_embeds=pe)
+    with pytest.raises(F.LvqError), torch.no_grad():
+        m.embeddings(x, pe)                                                     # fused with pre_layrnorm: VitModel.embed
+    for sub in (m.transformer.layers[0].mlp, m.transformer.layers[0].self_attn, m.transformer.layers[0], m.transformer):
+        with pytest.raises(F.LvqError), torch.no_grad():
+            sub(torch.zeros(1, 5, 128))
+
+
+def test_runtime_golden_is_data_only():
+    g = np.load(os.path.join(GOLDEN, "deepencoder_runtime.npz"))
+    assert g["out"].shape == (256 // CC.RUNTIME_ROW_STEP, 2048) and list(g["full_shape"]) == [256, 2048]
+    assert list(g["result_keys"]) == ["grid", "image_size", "tokens"]
+    assert VC.state_shapes(CC.RUNTIME_SAM)[0][0] == "pos_embed"
