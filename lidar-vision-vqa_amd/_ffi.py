@@ -202,6 +202,35 @@ def workspace(nbytes: int, device, tag: str, *, per_stream: bool = False, floor:
     return buf
 
 
+def version_of(tensors, extra=()) -> tuple:
+    """Identity of what was derived from `tensors`: (data_ptr, _version, shape, device) of every non-None one, then `extra` (whatever
+    else the derived value depends on and should REPLACE it when it changes: a mode, a flag, an eps).  In-place updates, load_state_dict,
+    a replaced .data, .to() / .double() and a view of another shape all change it.  Known limit: a train()-mode BatchNorm forward
+    updates running_mean / running_var in place without moving their _version (seen on the CPU; unmeasured on ROCm), so a fold made
+    before it is served after it -- the kernels run eval() models only."""
+    return tuple([(t.data_ptr(), t._version, t.shape, t.device) for t in tensors if t is not None]) + tuple(extra)
+
+
+def derived(cache: dict, key, tensors, build, extra=()):
+    """The one rule for values that depend on weights alone: cache[key] = (version, value), served while version_of(tensors, extra) is
+    what it was stored under, else rebuilt by build().  What goes into `key` is kept side by side, what goes into `extra` replaces the
+    entry.  A build() that raises leaves the entry as it was."""
+    ver = version_of(tensors, extra)
+    hit = cache.get(key)
+    if hit is not None and hit[0] == ver:
+        return hit[1]
+    val = build()
+    cache[key] = (ver, val)
+    return val
+
+
+def fold_batchnorm(bn):
+    """An eval()-mode BatchNorm as a per-channel affine -> (scale, shift), fp32."""
+    scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
+    shift = bn.bias.detach().float() - bn.running_mean.float() * scale
+    return scale.contiguous(), shift.contiguous()
+
+
 def attention_relpos_plan(gh: int, gw: int, precision: int):
     """lvq_attention_relpos_plan (host only, a hook for tests): (K | V stages, dynamic LDS bytes) of the kernel that the fused
     relative-position attention launches on a gh x gw grid; precision 1 = plain bf16, 3 = hi + lo."""

@@ -26,6 +26,7 @@ import torch.nn as nn
 
 from . import _ffi as F
 from . import autograd_route as AG
+from . import ops
 
 MODES = ("bf16x3", "bf16")
 DEFAULT_MODE = "bf16x3"
@@ -81,38 +82,18 @@ class _Layer:
 
     def packed(self, split: bool):
         p = self.conv.weight
-        ver = (p.data_ptr(), p._version, tuple(p.shape), p.device)
-        hit = self._cache.get(("w", split))
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        L = _lib()
-        k = self.stride if self.transposed else self.kernel
-        n = L.lvq_conv2d_packed_elems(self.c_out, self.c_in, k, int(self.transposed))
-        if n == 0:
-            raise F.LvqError(f"lvq_conv2d: {type(self.conv).__name__}({self.c_in} -> {self.c_out}, kernel {self.kernel}, stride {self.stride}) is "
-                             f"outside the kernel family ({FAMILY})")
-        w = p.detach().float().contiguous()
-        hi = torch.empty((n,), dtype=torch.int16, device=w.device)
-        lo = torch.empty((n,), dtype=torch.int16, device=w.device) if split else None
-        F.check(L.lvq_conv2d_pack_weights(F.ptr(w), self.c_out, self.c_in, k, int(self.transposed), F.ptr(hi),
-                                          F.ptr(lo), F.stream_ptr(w.device)), "lvq_conv2d_pack_weights")
-        self._cache[("w", split)] = (ver, (hi, lo))
-        return hi, lo
+
+        def build():
+            hi, lo = ops.conv2d_pack_weights(p.detach().float().contiguous(), self.c_out, self.c_in, self.stride if self.transposed else self.kernel,
+                                             self.transposed, split)
+            return hi.view(torch.int16), None if lo is None else lo.view(torch.int16)
+        return F.derived(self._cache, ("w", split), (p,), build)
 
     def folded(self):
         bn = self.bn
         if bn is None:
             return None, None
-        src = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        ver = tuple((t.data_ptr(), t._version, t.device) for t in src) + (bn.eps,)
-        hit = self._cache.get("bn")
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
-        shift = bn.bias.detach().float() - bn.running_mean.float() * scale
-        out = (scale.contiguous(), shift.contiguous())
-        self._cache["bn"] = (ver, out)
-        return out
+        return F.derived(self._cache, "bn", (bn.weight, bn.bias, bn.running_mean, bn.running_var), lambda: F.fold_batchnorm(bn), (bn.eps,))
 
     def run(self, x: Planes, split: bool, pad: int = 0, planes: Optional[Planes] = None, f32: Optional[torch.Tensor] = None,
             c_off: int = 0) -> Optional[Planes]:

@@ -125,11 +125,9 @@ class _SparseConv(nn.Module):
 
     # ---- caches (per parameter version and precision mode) ----
     def _packed(self, split: bool):
-        p = self.weight
-        ver = (p.data_ptr(), p._version, tuple(p.shape), p.device)
-        hit = self._cache.get(("w", split))
-        if hit is not None and hit[0] == ver:
-            return hit[1]
+        return F.derived(self._cache, ("w", split), (self.weight,), lambda: self._pack(split))
+
+    def _pack(self, split: bool):
         L = _lib()
         kvol = 1
         for k in self.kernel_size:
@@ -138,25 +136,15 @@ class _SparseConv(nn.Module):
         if n == 0:
             raise F.LvqError(f"lvq_sparse_conv: channels ({self.in_channels} -> {self.out_channels}) outside the kernel family "
                              "(C_in in 4, 5, 16, 32, 64, 128; C_out in 16, 32, 64, 128)")
-        w = p.detach().float().contiguous()
+        w = self.weight.detach().float().contiguous()
         hi = torch.empty((n,), dtype=torch.int16, device=w.device)
         lo = torch.empty((n,), dtype=torch.int16, device=w.device) if split else None
         F.check(L.lvq_sparse_conv_pack_weights(F.ptr(w), self.out_channels, kvol, self.in_channels, F.ptr(hi), F.ptr(lo),
                                                F.stream_ptr(w.device)), "lvq_sparse_conv_pack_weights")
-        self._cache[("w", split)] = (ver, (hi, lo))
         return hi, lo
 
     def _folded(self, bn: nn.BatchNorm1d):
-        src = [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-        ver = tuple((t.data_ptr(), t._version, t.device) for t in src) + (bn.eps,)
-        hit = self._cache.get(("bn", id(bn)))
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.float() + bn.eps)
-        shift = bn.bias.detach().float() - bn.running_mean.float() * scale
-        out = (scale.contiguous(), shift.contiguous())
-        self._cache[("bn", id(bn))] = (ver, out)
-        return out
+        return F.derived(self._cache, ("bn", id(bn)), (bn.weight, bn.bias, bn.running_mean, bn.running_var), lambda: F.fold_batchnorm(bn), (bn.eps,))
 
     def _rules(self, x: SparseConvTensor):
         key = self.indice_key

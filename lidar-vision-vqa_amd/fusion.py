@@ -59,17 +59,13 @@ class _HipModule(nn.Module):
     def _w(self, p: torch.Tensor, pad_k: int = 0) -> BF:
         """bf16 (hi[, lo]) copy of a weight matrix [N,K]; rebuilt when the parameter changes."""
         split = self._split()
-        key = (id(p), split)
-        ver = (p.data_ptr(), p._version, tuple(p.shape), p.device)
-        hit = self._wcache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        w = p.detach().reshape(p.shape[0], -1).float()
-        if pad_k and w.shape[1] % pad_k:
-            w = torch.nn.functional.pad(w, (0, pad_k - w.shape[1] % pad_k))
-        bf = ops.cast(w.contiguous(), split)
-        self._wcache[key] = (ver, bf)
-        return bf
+
+        def build():
+            w = p.detach().reshape(p.shape[0], -1).float()
+            if pad_k and w.shape[1] % pad_k:
+                w = torch.nn.functional.pad(w, (0, pad_k - w.shape[1] % pad_k))
+            return ops.cast(w.contiguous(), split)
+        return F.derived(self._wcache, (id(p), split), (p,), build)
 
     def _guard(self, *tensors):
         """The HIP route: eval() under no_grad() on CUDA tensors, or a loud error (callers ask _autograd() first)."""
@@ -210,14 +206,7 @@ class VATBlock(_HipModule):
 
     def _ca_blob(self, f16: bool) -> torch.Tensor:
         params = (self.ca_ln.weight, self.ca_ln.bias, self.ca.in_proj_weight, self.ca.in_proj_bias, self.ca.out_proj.weight, self.ca.out_proj.bias)
-        ver = tuple((p.data_ptr(), p._version, p.device) for p in params)
-        key = ("ca_fused", f16)
-        hit = self._wcache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        blob = ops.ca_fused_pack(*[_f32(p) for p in params], self.n_heads, f16)
-        self._wcache[key] = (ver, blob)
-        return blob
+        return F.derived(self._wcache, ("ca_fused", f16), params, lambda: ops.ca_fused_pack(*[_f32(p) for p in params], self.n_heads, f16))
 
     def _cross_attn_fused(self, q2: torch.Tensor, kv: torch.Tensor, B: int, nq: int, f16: bool) -> torch.Tensor:
         out = ops.ca_fused(q2.view(B, nq, self.d_model), kv, self._ca_blob(f16), self.ca_ln.eps, self.n_heads, f16, tag="ca_fused")
@@ -327,23 +316,37 @@ class VATLiDAR(_HipModule):
             self._cache[key] = (geom.to(device), sid.to(device))
         return self._cache[key]
 
+    # ---- what the cached, input-independent values are derived from: each group of parameters is named once ----
+    def _pe_params(self) -> List[torch.Tensor]:
+        """The positional table's five."""
+        return [self.geo_mlp[0].weight, self.geo_mlp[0].bias, self.geo_mlp[2].weight, self.geo_mlp[2].bias, self.view_embed]
+
+    def _table_params(self) -> List[torch.Tensor]:
+        """Everything the K|V table of the empty scene reads: refine conv, token projection and LayerNorm, the positional table (eleven
+        tensors) and every block's K|V projection."""
+        params = [self.refine[0].weight, self.refine[0].bias, self.proj.weight, self.proj.bias, self.norm_tokens.weight, self.norm_tokens.bias]
+        params += self._pe_params()
+        for blk in self.blocks:
+            params += [blk.ca.in_proj_weight, blk.ca.in_proj_bias]
+        return params
+
+    def _query_params(self, blk: "VATBlock") -> List[torch.Tensor]:
+        """Everything a block's shared query side reads: the learned queries and the block's self-attention and Q projection (twelve)."""
+        return [self.query, self.view_embed, blk.sa_ln.weight, blk.sa_ln.bias, blk.sa.in_proj_weight, blk.sa.in_proj_bias, blk.sa.out_proj.weight,
+                blk.sa.out_proj.bias, blk.ca_ln.weight, blk.ca_ln.bias, blk.ca.in_proj_weight, blk.ca.in_proj_bias]
+
     def _pe_table(self, H: int, W: int, device) -> torch.Tensor:
         """geo_mlp(geom) + view_embed[sid]: [HW, d] fp32, input-independent -> cached per weights version."""
         split = self._split()
-        params = (self.geo_mlp[0].weight, self.geo_mlp[0].bias, self.geo_mlp[2].weight, self.geo_mlp[2].bias, self.view_embed)
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (split,)
-        key = (H, W, device)
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        geom, sid = self._grid(H, W, device)
-        g8 = torch.nn.functional.pad(geom, (0, 3)).contiguous()            # K = 5 -> 8 (zero columns)
-        _, h1 = ops.linear(ops.cast(g8, split), self._w(self.geo_mlp[0].weight, pad_k=8), self.geo_mlp[0].bias, gelu=True,
-                           out_bf=True)
-        ve = self.view_embed.detach().float()[sid].contiguous()            # gather of a 6-row table (index plumbing)
-        pe, _ = ops.linear(h1, self._w(self.geo_mlp[2].weight), self.geo_mlp[2].bias, residual=ve, out_f32=True)
-        self._pe_cache[key] = (ver, pe)
-        return pe
+
+        def build():
+            geom, sid = self._grid(H, W, device)
+            g8 = torch.nn.functional.pad(geom, (0, 3)).contiguous()            # K = 5 -> 8 (zero columns)
+            _, h1 = ops.linear(ops.cast(g8, split), self._w(self.geo_mlp[0].weight, pad_k=8), self.geo_mlp[0].bias, gelu=True,
+                               out_bf=True)
+            ve = self.view_embed.detach().float()[sid].contiguous()            # gather of a 6-row table (index plumbing)
+            return ops.linear(h1, self._w(self.geo_mlp[2].weight), self.geo_mlp[2].bias, residual=ve, out_f32=True)[0]
+        return F.derived(self._pe_cache, (H, W, device), self._pe_params(), build, (split,))
 
     def bev_tokens(self, bev: torch.Tensor) -> BF:
         """vat_lidar.py:212-248: refine -> proj -> LayerNorm -> + geo PE + view embed; BF [B*HW, d]."""
@@ -385,14 +388,11 @@ class VATLiDAR(_HipModule):
     def _pe_tiled(self, H: int, W: int, dev) -> torch.Tensor:
         """The positional table with its rows in the key order of the tiled stream: tile t (8 x 8 cells) major, then piece p = 2 (y >> 1)
         + (x >> 2) (2 x 4 cells), then 4 (y & 1) + (x & 3) inside the piece -- a permutation of _pe_table."""
-        pe = self._pe_table(H, W, dev)
-        hit = self._pe_cache.get(("tiled", H, W, dev))
-        if hit is not None and hit[0] is pe:
-            return hit[1]
-        d = pe.shape[1]
-        pt = pe.view(H // 8, 4, 2, W // 8, 2, 4, d).permute(0, 3, 1, 4, 2, 5, 6).reshape(H * W, d).contiguous()
-        self._pe_cache[("tiled", H, W, dev)] = (pe, pt)
-        return pt
+
+        def build():
+            pe = self._pe_table(H, W, dev)
+            return pe.view(H // 8, 4, 2, W // 8, 2, 4, pe.shape[1]).permute(0, 3, 1, 4, 2, 5, 6).reshape(H * W, -1).contiguous()
+        return F.derived(self._pe_cache, ("tiled", H, W, dev), self._pe_params(), build, (self._split(),))
 
     def _tile_tokens(self, feat, idx, live, dirty, counts, cap_rows, batch, H, W) -> BF:
         C = feat.shape[1]
@@ -406,50 +406,42 @@ class VATLiDAR(_HipModule):
         -> (R BF [64, 64], r0 [64], c0, per layer (M BF [2d, 64], m0 [2d], T [HW, 2d] fp32 in tile-major key order)), cached per weights
         version and precision mode.  The small factors are folded in fp64 (model-load-time plumbing, like folding a BatchNorm); the
         table T runs through lvq_gemm_bf16 in the mode's operand form."""
-        params = [self.proj.weight, self.proj.bias, self.norm_tokens.weight, self.norm_tokens.bias, self.geo_mlp[0].weight, self.geo_mlp[0].bias,
-                  self.geo_mlp[2].weight, self.geo_mlp[2].bias, self.view_embed]
-        for blk in self.blocks:
-            params += [blk.ca.in_proj_weight, blk.ca.in_proj_bias]
         t16 = bool(os.environ.get("LVQ_KV_T_FP16")) and not os.environ.get("LVQ_KV_ONE_LAUNCH")    # opt-in fp16 table (two-launch form only)
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (self._mode(), t16)
-        key = ("kv_fold", H, W, dev)
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        split = self._split()
-        d = self.d_model
-        f64 = lambda p: p.detach().to(device="cpu", dtype=torch.float64)      # the small factors: host fp64 (a 768 x 65 QR, two thin products)
-        wp, bp = f64(self.proj.weight).view(d, C), f64(self.proj.bias)
-        wc, bc = wp - wp.mean(0, keepdim=True), bp - bp.mean()
-        rr = torch.linalg.qr(torch.cat((wc, bc[:, None]), 1), mode="r").R          # [C + 1, C + 1]: |Wc t + bc|^2 = |R [t; 1]|^2
-        r_bf = ops.cast(rr[:C, :C].float().contiguous().to(dev), split)
-        r0 = rr[:C, C].float().contiguous().to(dev)
-        c0 = float(rr[C, C] ** 2)
-        gam, bet = f64(self.norm_tokens.weight), self.norm_tokens.bias.detach().float().view(1, d).contiguous()
-        a_pe = ops.cast(ops.scale_add_rows(self._pe_tiled(H, W, dev), bet), split)  # beta + PE[key], the A operand of the table GEMM
-        # |LayerNorm(y)_n| <= sqrt(d) whatever the input, so |x_n| <= sqrt(d) |gamma_n| + |beta_n| + max_key |PE_n| and every K entry of
-        # layer 0 is bounded by its weight row's L1 product with that: the static guarantee behind the fp16 K half of "mixed16"
-        xmax = (math.sqrt(d) * gam.abs() + f64(self.norm_tokens.bias).abs() + self._pe_tiled(H, W, dev).abs().amax(0).double().cpu())
-        wk0, bk0 = f64(self.blocks[0].ca.in_proj_weight)[d:2 * d], f64(self.blocks[0].ca.in_proj_bias)[d:2 * d]
-        k_bound = float((wk0.abs() @ xmax + bk0.abs()).max())
-        layers = []
-        for blk in self.blocks:
-            blk.precision = self.precision
-            wkv = f64(blk.ca.in_proj_weight)[d:]
-            m_bf = ops.cast((wkv @ (gam[:, None] * wc)).float().contiguous().to(dev), split)
-            m0 = (wkv @ (gam * bc)).float().contiguous().to(dev)
-            t_tab, _ = ops.linear(a_pe, blk._w(blk.ca.in_proj_weight), blk.ca.in_proj_bias, out_f32=True, w_rows=(d, 3 * d))
-            # the table as fp16 when its values fit (checked once, here): its 2^-12 rounding disappears under the bf16 rounding of the
-            # rows, and the kernel's largest read stream halves (two-launch form only; dtype conversion = plumbing)
-            # LVQ_KV_T_FP16=1: the table as IEEE fp16 (values checked here) -- half the bytes of k_kv_rows' largest read stream, 4.5 -> 3.8 ms,
-            # +4 % tokens/s.  Opt-in, because it is not free: rounding T to 11 bits moves the fused tokens by 1.4e-4 (1.04e-4 -> 2.4e-4 against
-            # the oracle; linear in the rounding -- bf16 would cost 1.5e-3 -- and mostly through the V half: DESIGN 3.3)
-            if t16 and float(t_tab.abs().max()) < 3.0e4:
-                t_tab = t_tab.to(torch.float16)
-            layers.append((m_bf, m0, t_tab))
-        fold = (r_bf, r0, c0, layers, k_bound)
-        self._pe_cache[key] = (ver, fold)
-        return fold
+
+        def build():
+            split = self._split()
+            d = self.d_model
+            f64 = lambda p: p.detach().to(device="cpu", dtype=torch.float64)      # the small factors: host fp64 (a 768 x 65 QR, two thin products)
+            wp, bp = f64(self.proj.weight).view(d, C), f64(self.proj.bias)
+            wc, bc = wp - wp.mean(0, keepdim=True), bp - bp.mean()
+            rr = torch.linalg.qr(torch.cat((wc, bc[:, None]), 1), mode="r").R          # [C + 1, C + 1]: |Wc t + bc|^2 = |R [t; 1]|^2
+            r_bf = ops.cast(rr[:C, :C].float().contiguous().to(dev), split)
+            r0 = rr[:C, C].float().contiguous().to(dev)
+            c0 = float(rr[C, C] ** 2)
+            gam, bet = f64(self.norm_tokens.weight), self.norm_tokens.bias.detach().float().view(1, d).contiguous()
+            a_pe = ops.cast(ops.scale_add_rows(self._pe_tiled(H, W, dev), bet), split)  # beta + PE[key], the A operand of the table GEMM
+            # |LayerNorm(y)_n| <= sqrt(d) whatever the input, so |x_n| <= sqrt(d) |gamma_n| + |beta_n| + max_key |PE_n| and every K entry of
+            # layer 0 is bounded by its weight row's L1 product with that: the static guarantee behind the fp16 K half of "mixed16"
+            xmax = (math.sqrt(d) * gam.abs() + f64(self.norm_tokens.bias).abs() + self._pe_tiled(H, W, dev).abs().amax(0).double().cpu())
+            wk0, bk0 = f64(self.blocks[0].ca.in_proj_weight)[d:2 * d], f64(self.blocks[0].ca.in_proj_bias)[d:2 * d]
+            k_bound = float((wk0.abs() @ xmax + bk0.abs()).max())
+            layers = []
+            for blk in self.blocks:
+                blk.precision = self.precision
+                wkv = f64(blk.ca.in_proj_weight)[d:]
+                m_bf = ops.cast((wkv @ (gam[:, None] * wc)).float().contiguous().to(dev), split)
+                m0 = (wkv @ (gam * bc)).float().contiguous().to(dev)
+                t_tab, _ = ops.linear(a_pe, blk._w(blk.ca.in_proj_weight), blk.ca.in_proj_bias, out_f32=True, w_rows=(d, 3 * d))
+                # the table as fp16 when its values fit (checked once, here): its 2^-12 rounding disappears under the bf16 rounding of the
+                # rows, and the kernel's largest read stream halves (two-launch form only; dtype conversion = plumbing)
+                # LVQ_KV_T_FP16=1: the table as IEEE fp16 (values checked here) -- half the bytes of k_kv_rows' largest read stream, 4.5 -> 3.8 ms,
+                # +4 % tokens/s.  Opt-in, because it is not free: rounding T to 11 bits moves the fused tokens by 1.4e-4 (1.04e-4 -> 2.4e-4 against
+                # the oracle; linear in the rounding -- bf16 would cost 1.5e-3 -- and mostly through the V half: DESIGN 3.3)
+                if t16 and float(t_tab.abs().max()) < 3.0e4:
+                    t_tab = t_tab.to(torch.float16)
+                layers.append((m_bf, m0, t_tab))
+            return r_bf, r0, c0, layers, k_bound
+        return F.derived(self._pe_cache, ("kv_fold", H, W, dev), self._table_params(), build, (self._mode(), t16))
 
     def _tile_kv(self, li: int, feat, idx, live, dirty, counts, cap_rows, batch, H, W, out, k_fp16: bool = False) -> None:
         C = feat.shape[1]
@@ -463,44 +455,37 @@ class VATLiDAR(_HipModule):
         """Per layer ONE K|V buffer [HW + batch*HW, 2d] bf16.  Rows 0 .. HW-1: the per-model TABLE = K|V of the EMPTY scene by the same
         kernel that serves the dirty rows (every cell forced dirty; key order = tile-major), cached per weights version and precision
         mode -- input-independent like the positional table.  Rows HW ..: the step's computed rows (capacity for `batch` scenes)."""
-        params = [self.refine[0].weight, self.refine[0].bias, self.proj.weight, self.proj.bias, self.norm_tokens.weight, self.norm_tokens.bias,
-                  self.geo_mlp[0].weight, self.geo_mlp[0].bias, self.geo_mlp[2].weight, self.geo_mlp[2].bias, self.view_embed]
-        for blk in self.blocks:
-            params += [blk.ca.in_proj_weight, blk.ca.in_proj_bias]
         fused = not os.environ.get("LVQ_NO_FUSED_KV")
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (self._mode(), fused, k16, bool(os.environ.get("LVQ_KV_ONE_LAUNCH")),
-                                                                   bool(os.environ.get("LVQ_KV_T_FP16")))
         key = ("kv_buffer", H, W, dev)
         hw, d = H * W, self.d_model
         rows = hw + batch * hw
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            if hit[1][0].shape[0] >= rows:
-                return hit[1]
+
+        def build():
+            # a new table: whatever was derived from the old one (block 0's softmax totals) goes with it -- content identity is the
+            # version tuple, never the buffer address (a freed block can come back from the allocator with other contents)
+            self._pe_cache.pop(("signed_totals", H, W, dev), None)
+            idx = torch.full((1, H, W), -1, dtype=torch.int32, device=dev)
+            live, dirty, src, counts = ops.bev_tiles(idx, 1, H, W, dev, 0, force_all=True)
+            feat = torch.zeros((1, C), dtype=torch.float32, device=dev)
+            x = None if fused else self._tile_tokens(feat, idx, live, dirty, counts, hw, 1, H, W)
             bufs = []
-            for old in hit[1]:                                  # a larger batch: new buffers, the table rows copied over
+            for li, blk in enumerate(self.blocks):
+                blk.precision = self.precision
                 buf = torch.empty((rows, 2 * d), dtype=torch.bfloat16, device=dev)
-                buf[:hw].copy_(old[:hw])
+                if fused:
+                    self._tile_kv(li, feat, idx, live, dirty, counts, hw, 1, H, W, buf[:hw], k_fp16=k16 and li == 0)
+                else:
+                    ops.linear_live_rows(x, blk._w(blk.ca.in_proj_weight), blk.ca.in_proj_bias, counts[2:], (d, 3 * d), out=buf[:hw])
                 bufs.append(buf)
-            self._pe_cache[key] = (ver, bufs)
             return bufs
-        # a new table: whatever was derived from the old one (block 0's softmax totals) goes with it -- content identity is the
-        # version tuple, never the buffer address (a freed block can come back from the allocator with other contents)
-        self._pe_cache.pop(("signed_totals", H, W, dev), None)
-        idx = torch.full((1, H, W), -1, dtype=torch.int32, device=dev)
-        live, dirty, src, counts = ops.bev_tiles(idx, 1, H, W, dev, 0, force_all=True)
-        feat = torch.zeros((1, C), dtype=torch.float32, device=dev)
-        x = None if fused else self._tile_tokens(feat, idx, live, dirty, counts, hw, 1, H, W)
-        bufs = []
-        for li, blk in enumerate(self.blocks):
-            blk.precision = self.precision
-            buf = torch.empty((rows, 2 * d), dtype=torch.bfloat16, device=dev)
-            if fused:
-                self._tile_kv(li, feat, idx, live, dirty, counts, hw, 1, H, W, buf[:hw], k_fp16=k16 and li == 0)
-            else:
-                ops.linear_live_rows(x, blk._w(blk.ca.in_proj_weight), blk.ca.in_proj_bias, counts[2:], (d, 3 * d), out=buf[:hw])
-            bufs.append(buf)
-        self._pe_cache[key] = (ver, bufs)
+        bufs = F.derived(self._pe_cache, key, self._table_params(), build,
+                         (self._mode(), fused, k16, bool(os.environ.get("LVQ_KV_ONE_LAUNCH")), bool(os.environ.get("LVQ_KV_T_FP16"))))
+        if bufs[0].shape[0] < rows:                             # a larger batch: new buffers under the unchanged version, the table rows copied over
+            grown = [torch.empty((rows, 2 * d), dtype=torch.bfloat16, device=dev) for _ in bufs]
+            for buf, old in zip(grown, bufs):
+                buf[:hw].copy_(old[:hw])
+            self._pe_cache[key] = (self._pe_cache[key][0], grown)
+            return grown
         return bufs
 
     def _query_side(self, blk: "VATBlock", dev) -> Tuple[torch.Tensor, BF]:
@@ -508,30 +493,14 @@ class VATLiDAR(_HipModule):
         computed once per weights version, precision mode and device (about eight dependent launches off every step).  Same kernels on the
         same inputs give the same bits, so the cached pair is what a fresh call would return and the cached `totals` stay its totals.
         Both tensors are read-only downstream (residual / attention operands, the guard's audit)."""
-        params = [self.query, self.view_embed, blk.sa_ln.weight, blk.sa_ln.bias, blk.sa.in_proj_weight, blk.sa.in_proj_bias, blk.sa.out_proj.weight,
-                  blk.sa.out_proj.bias, blk.ca_ln.weight, blk.ca_ln.bias, blk.ca.in_proj_weight, blk.ca.in_proj_bias]
-        ver = tuple((p.data_ptr(), p._version) for p in params)
-        key = ("query_side", blk._mode(), dev)
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        pair = blk.shared_query_side(self._queries(1), self.n_queries)
-        self._pe_cache[key] = (ver, pair)
-        return pair
+        return F.derived(self._pe_cache, ("query_side", blk._mode(), dev), self._query_params(blk),
+                         lambda: blk.shared_query_side(self._queries(1), self.n_queries))
 
     def _q16_ok(self, blk: "VATBlock", qp: BF) -> bool:
         """mixed16: the scaled queries of block 0 fit fp16 (they depend on the weights only: checked once per weights version)."""
-        params = [self.query, self.view_embed, blk.sa_ln.weight, blk.sa_ln.bias, blk.sa.in_proj_weight, blk.sa.in_proj_bias, blk.sa.out_proj.weight,
-                  blk.sa.out_proj.bias, blk.ca_ln.weight, blk.ca_ln.bias, blk.ca.in_proj_weight, blk.ca.in_proj_bias]
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (self._mode(),)
-        hit = self._pe_cache.get("q16_ok")
-        if hit is not None and hit[0] == ver:
-            return hit[1]
         dh = blk.d_model // blk.n_heads
-        qmax = float(ops.to_f32(qp).abs().max()) * (1.0 / math.sqrt(dh)) * 1.4426950408889634
-        ok = qmax < 3.0e4
-        self._pe_cache["q16_ok"] = (ver, ok)
-        return ok
+        return F.derived(self._pe_cache, "q16_ok", self._query_params(blk),
+                         lambda: float(ops.to_f32(qp).abs().max()) * (1.0 / math.sqrt(dh)) * 1.4426950408889634 < 3.0e4, (self._mode(),))
 
     # ---- guard of the plain-bf16 key stream (the "mixed" modes): DESIGN 3.3 ----
     STREAM_GUARD_MAX = 0.5     # max over (head, query) of (1 + max |score|) / sqrt(N_eff); tools/mixed_guard_study.py: 0.04 on the bench model
@@ -543,28 +512,20 @@ class VATLiDAR(_HipModule):
         roundings average out over the keys that carry the softmax mass; when the model's attention is peaked (few keys carry it, large
         scores) they do not, and the modes that rely on it run the hi + lo route instead (forward_pillars).  Once per weights version."""
         blk = self.blocks[0]
-        params = [self.query, self.view_embed, blk.sa_ln.weight, blk.sa_ln.bias, blk.sa.in_proj_weight, blk.sa.in_proj_bias, blk.sa.out_proj.weight,
-                  blk.sa.out_proj.bias, blk.ca_ln.weight, blk.ca_ln.bias, blk.ca.in_proj_weight, blk.ca.in_proj_bias,
-                  self.refine[0].weight, self.refine[0].bias, self.proj.weight, self.proj.bias, self.norm_tokens.weight, self.norm_tokens.bias,
-                  self.geo_mlp[0].weight, self.geo_mlp[0].bias, self.geo_mlp[2].weight, self.geo_mlp[2].bias]
-        ver = tuple((p.data_ptr(), p._version) for p in params)
-        key = ("stream_guard", H, W, dev)
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
-        keep = self.precision
-        try:
-            self.precision = "mixed"                           # the statistic is taken on the stream it guards: the plain table of the mixed mode
-            blk.precision = "mixed"
-            _, qp = self._query_side(blk, dev)                 # cached under the mode forced here, not the caller's
-            table = self._kv_buffers(C, H, W, dev, 1, False)[0]
-            dh = blk.d_model // blk.n_heads
-            g = float(ops.stream_guard(qp[0], table[:H * W], blk.n_heads, 1.0 / math.sqrt(dh)).max())
-        finally:
-            self.precision = keep
-            blk.precision = keep
-        self._pe_cache[key] = (ver, g)
-        return g
+
+        def build():
+            keep = self.precision
+            try:
+                self.precision = "mixed"                       # the statistic is taken on the stream it guards: the plain table of the mixed mode
+                blk.precision = "mixed"
+                _, qp = self._query_side(blk, dev)             # cached under the mode forced here, not the caller's
+                table = self._kv_buffers(C, H, W, dev, 1, False)[0]
+                dh = blk.d_model // blk.n_heads
+                return float(ops.stream_guard(qp[0], table[:H * W], blk.n_heads, 1.0 / math.sqrt(dh)).max())
+            finally:
+                self.precision = keep
+                blk.precision = keep
+        return F.derived(self._pe_cache, ("stream_guard", H, W, dev), self._query_params(blk) + self._table_params(), build)
 
     def guard_counters(self) -> Tuple[int, int, float]:
         """Per-launch half of the guard, accumulated since the module was created (reads the device: a synchronisation): (rows whose
@@ -619,24 +580,18 @@ class VATLiDAR(_HipModule):
         """Softmax sums of block 0's (scene-independent) cross-attention queries over ALL keys of the K|V table -> fp32
         [heads, nq, 66]; input-independent like the table itself, cached per weights version.  `qp` is this step's Q projection:
         the cached totals belong to exactly these bits as long as the version key is unchanged."""
-        params = [self.query, self.view_embed, blk.sa_ln.weight, blk.sa_ln.bias, blk.sa.in_proj_weight, blk.sa.in_proj_bias, blk.sa.out_proj.weight,
-                  blk.sa.out_proj.bias, blk.ca_ln.weight, blk.ca_ln.bias, blk.ca.in_proj_weight, blk.ca.in_proj_bias]
         # the table side of the totals: the version tuple of the K|V buffers they were computed from (all table-side parameters,
         # precision mode, fused / k16 / route flags -- _kv_buffers), not the buffer's address
         kv_hit = self._pe_cache.get(("kv_buffer", H, W, dev))
-        kv_ver = kv_hit[0] if kv_hit is not None and any(b is kv for b in kv_hit[1]) else ("unversioned", kv.data_ptr(), kv._version)
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (self._mode(), kv_ver, k_fp16, bool(os.environ.get("LVQ_TOTALS_Q16")))
-        key = ("signed_totals", H, W, dev)
-        hit = self._pe_cache.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1]
+        kv_ver = kv_hit[0] if kv_hit is not None and any(b is kv for b in kv_hit[1]) else ("unversioned",) + F.version_of((kv,))
         dh = blk.d_model // blk.n_heads
+        q16 = bool(os.environ.get("LVQ_TOTALS_Q16"))
         # mixed16: the totals keep the full query (fp16 hi + lo against the fp16 table keys, k_fp16 = 2) unless LVQ_TOTALS_Q16 asks for the
         # once-rounded query of the per-scene streams
-        tot = ops.attention_stream_totals(qp, kv[:H * W], n_heads=blk.n_heads, nq=self.n_queries, nkv=H * W, dh=dh, scale=1.0 / math.sqrt(dh),
-                                          k_fp16=(1 if os.environ.get("LVQ_TOTALS_Q16") else 2) if k_fp16 else 0)
-        self._pe_cache[key] = (ver, tot)
-        return tot
+        return F.derived(self._pe_cache, ("signed_totals", H, W, dev), self._query_params(blk),
+                         lambda: ops.attention_stream_totals(qp, kv[:H * W], n_heads=blk.n_heads, nq=self.n_queries, nkv=H * W, dh=dh,
+                                                             scale=1.0 / math.sqrt(dh), k_fp16=(1 if q16 else 2) if k_fp16 else 0),
+                         (self._mode(), kv_ver, k_fp16, q16))
 
     def forward_pillars(self, pillar_features: torch.Tensor, coords_bzyx: torch.Tensor, n_live: Optional[torch.Tensor],
                         batch: int, H: int, W: int, all_tiles_live: bool = False) -> torch.Tensor:
@@ -717,7 +672,7 @@ class VATLiDAR(_HipModule):
         return _post_head(self, q2, self.final_ln, self.post).view(batch, self.n_queries, self.d_model)
 
     def _guard_version(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+        return F.version_of(self.parameters())
 
     def _forward_pillars_hilo(self, pillar_features, coords_bzyx, n_live, batch, H, W, all_tiles_live):
         keep = self.precision

@@ -150,14 +150,11 @@ class StandInHead(_HipModule):
     def _pack(self, key, params, biases=None):
         """Concatenated projection weights (q|k|v, gate|up) as one GEMM operand; rebuilt when a member changes."""
         split = self._split()
-        ver = tuple((p.data_ptr(), p._version) for p in params) + (split,)
-        hit = self._packed.get(key)
-        if hit is not None and hit[0] == ver:
-            return hit[1], hit[2]
-        w = ops.cast(torch.cat([p.detach().float() for p in params], dim=0).contiguous(), split)
-        b = torch.cat([p.detach().float() for p in biases]).contiguous() if biases else None
-        self._packed[key] = (ver, w, b)
-        return w, b
+
+        def build():
+            w = ops.cast(torch.cat([p.detach().float() for p in params], dim=0).contiguous(), split)
+            return w, (torch.cat([p.detach().float() for p in biases]).contiguous() if biases else None)
+        return F.derived(self._packed, key, params, build, (split,))
 
     def _layers(self, x: torch.Tensor, B: int, Lq: int, pos0: int = 0, cache=None) -> torch.Tensor:
         """The decoder stack on rows x [B*Lq, d] = positions pos0 .. pos0+Lq-1 of every sequence.  cache = None: plain causal
@@ -259,7 +256,7 @@ class StandInHead(_HipModule):
         return emb, lens.to(torch.int32).contiguous()
 
     def _weights_version(self):
-        return tuple((p.data_ptr(), p._version) for p in self.parameters())
+        return F.version_of(self.parameters())
 
     @torch.no_grad()
     def prefill_prefix(self, inputs_embeds: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> PrefixCache:

@@ -76,6 +76,20 @@ def cast(x: torch.Tensor, split: bool) -> BF:
     return hi, lo
 
 
+def conv2d_pack_weights(weight: torch.Tensor, c_out: int, c_in: int, k: int, transposed: bool, split: bool) -> BF:
+    """fp32 conv weights [c_out, c_in, k, k] (transposed: [c_in, c_out, k, k]) -> the packed bf16 (hi, lo) operand of lvq_conv2d /
+    lvq_deconv2d (once per weights version)."""
+    F.require_cuda(weight)
+    L = F.lib()
+    n = L.lvq_conv2d_packed_elems(c_out, c_in, k, int(transposed))
+    if n == 0:
+        raise F.LvqError(f"lvq_conv2d: {'ConvTranspose2d' if transposed else 'Conv2d'}({c_in} -> {c_out}, kernel {k}) is outside the kernel family")
+    hi, lo = _bf_empty((n,), weight.device, split)
+    F.check(L.lvq_conv2d_pack_weights(F.ptr(weight), c_out, c_in, k, int(transposed), F.ptr(hi), F.ptr(lo), F.stream_ptr(weight.device)),
+            "lvq_conv2d_pack_weights")
+    return hi, lo
+
+
 def to_f32(x: BF, alpha: float = 1.0) -> torch.Tensor:
     hi, lo = x
     out = torch.empty(hi.shape, dtype=torch.float32, device=hi.device)

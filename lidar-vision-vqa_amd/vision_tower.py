@@ -52,20 +52,9 @@ FAMILY = "use_rel_pos=True, head dim 64, attention grids (window, or image / pat
 # ------------------------------------------------------------------------------------------------------------------------------------
 # caches and guards
 # ------------------------------------------------------------------------------------------------------------------------------------
-def _version(*params):
-    return tuple((p.data_ptr(), p._version, tuple(p.shape), p.device) for p in params)
-
-
 def _cached(mod: nn.Module, key, params, build):
     """build() once per (key, version of params): packed weights and resized tables."""
-    cache = mod.__dict__.setdefault("_lvq_cache", {})
-    ver = _version(*params)
-    hit = cache.get(key)
-    if hit is not None and hit[0] == ver:
-        return hit[1]
-    val = build()
-    cache[key] = (ver, val)
-    return val
+    return F.derived(mod.__dict__.setdefault("_lvq_cache", {}), key, params, build)
 
 
 def _operand(mod: nn.Module, name: str, split: bool, shape=None) -> O.BF:
@@ -299,17 +288,8 @@ def _conv(conv: nn.Conv2d, x: O.BF, b: int, h: int, w: int, split: bool, planes:
     out32 = None if planes else torch.empty((b, c_out, oh, ow), dtype=torch.float32, device=dev)
     for c0 in range(0, c_out, 512):
         c1 = min(c_out, c0 + 512)
-
-        def pack():
-            n = L.lvq_conv2d_packed_elems(c1 - c0, c_in, k, 0)
-            if n == 0:
-                raise F.LvqError(f"lvq_conv2d: Conv2d({c_in} -> {c1 - c0}) is outside the kernel family")
-            wt = conv.weight.detach().float()[c0:c1].contiguous()
-            hi, lo = O._bf_empty((n,), dev, split)
-            F.check(L.lvq_conv2d_pack_weights(F.ptr(wt), c1 - c0, c_in, k, 0, F.ptr(hi), F.ptr(lo), F.stream_ptr(dev)),
-                    "lvq_conv2d_pack_weights")
-            return hi, lo
-        wh, wl = _cached(conv, ("conv", c0, c1, split), (conv.weight,), pack)
+        wh, wl = _cached(conv, ("conv", c0, c1, split), (conv.weight,),
+                         lambda: O.conv2d_pack_weights(conv.weight.detach().float()[c0:c1].contiguous(), c1 - c0, c_in, k, False, split))
         F.check(L.lvq_conv2d(F.ptr(x[0]), F.ptr(x[1]), b, h, w, c_in, F.ptr(wh), F.ptr(wl), c1 - c0,
                              k, s, F.ptr(None), F.ptr(None), 0, F.ptr(out_bf[0]), F.ptr(out_bf[1]), F.ptr(out32),
                              c_out, c0, F.stream_ptr(dev)), "lvq_conv2d")
