@@ -541,10 +541,12 @@ int lvq_sparse_to_dense(const float *feats, const int32_t *indices, int index_co
                         int c, int batch, int d, int h, int w, float *out, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
 /* =====================================================================================
- * Sparse convolution backbone (csrc/sparse_conv.hip): the layers of VoxelResBackBone8xVoxelNeXt
+ * Sparse convolution backbones (csrc/sparse_conv.hip): the layers of VoxelResBackBone8xVoxelNeXt, VoxelBackBone8x / VoxelResBackBone8x
+ * and PillarBackBone8x / PillarRes18BackBone8x
  * ===================================================================================== */
 
-/* Semantics (spconv 2.x, as pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225 uses it through pcdet/utils/spconv_utils.py:1-30).
+/* Semantics (spconv 2.x, as pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225, spconv_backbone.py:8-295 and spconv_backbone_2d.py:8-300
+ * use it through pcdet/utils/spconv_utils.py:1-30).
  *   tensor    features [N, C] fp32, indices [N, 1 + nd] int32 = (b, z, y, x) or (b, y, x), spatial_shape (D, H, W) or (H, W), batch.
  *             The index rows of one tensor are distinct (as spconv requires); a row outside the grid or the batch takes no part.
  *   weight    [C_out, kz, ky, kx, C_in] (2-D: [C_out, ky, kx, C_in]), spconv 2.x's layout.  The convolution is a CROSS-CORRELATION: it
@@ -552,7 +554,7 @@ int lvq_sparse_to_dense(const float *feats, const int32_t *indices, int index_co
  *   submanifold conv (SubMConv3d / SubMConv2d; odd kernel <= 3, stride 1): the output rows are the input rows, in the same order;
  *             out[i] = bias + sum_o W[:, o, :] . in[row(c_i + o - k/2)] over the offsets whose neighbour is an active row of the same
  *             scene inside the grid.  An absent neighbour contributes nothing.
- *   regular conv (SparseConv3d / SparseConv2d; kernel <= 3, stride s, padding p < k): output shape floor((D + 2p - k) / s) + 1 per
+ *   regular conv (SparseConv3d / SparseConv2d; kernel <= 3, stride s, padding p >= 0, each per axis): output shape floor((D + 2p - k) / s) + 1 per
  *             axis; site q is active iff some input q * s - p + o is active and inside the grid; out[q] = sum_o W[:, o, :] . in[row(q * s - p + o)].
  *             spconv leaves the order of the output rows unspecified; here they ascend in (b, z, y, x).  Everything downstream
  *             (lvq_sparse_bev_merge, lvq_sparse_to_dense, further rules) addresses rows through their coordinates.
@@ -590,8 +592,9 @@ int lvq_sparse_conv_rules(const int32_t *indices, int64_t n_in, int ndim, const 
  *                                  bias / scale + shift (both or neither) / residual [n_out_cap, c_out] may be NULL.  n_out_dev (device
  *                                  int32, may be NULL = all n_out_cap rows; clamped to n_out_cap): rows at and behind it are not written.
  *                                  A table entry outside [0, n_in) reads as absent.  No workspace.
- * c_in in {4, 5, 16, 32, 64, 128}, c_out in {16, 32, 64, 128}, k_vol <= 27; anything else returns LVQ_EUNSUPPORTED.  w_hi / w_lo 16-byte
- * aligned, feat 16-byte aligned when c_in % 4 == 0. */
+ * c_in in {4, 5, 16, 32, 64, 128} with c_out in {16, 32, 64, 128}, or the wide pairs (c_in, c_out) = (128, 256) and (256, 256); k_vol <= 27;
+ * anything else ((256, 128) included) returns LVQ_EUNSUPPORTED.  c_in = 256 is summed as two 128-channel stages per offset, ascending, so the
+ * order above holds.  w_hi / w_lo 16-byte aligned, feat 16-byte aligned when c_in % 4 == 0. */
 size_t lvq_sparse_conv_packed_elems(int c_out, int k_vol, int c_in);
 int lvq_sparse_conv_pack_weights(const float *weight, int c_out, int k_vol, int c_in, lvq_bf16 *w_hi, lvq_bf16 *w_lo, lvq_stream_t stream);
 int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nbr, int k_vol, int64_t n_out_cap, const int32_t *n_out_dev,
@@ -599,7 +602,7 @@ int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nb
                     const float *residual, int relu, float *out, lvq_stream_t stream);
 
 /* =====================================================================================
- * Dense 2-D BEV backbone (csrc/conv2d.hip): the layers of BaseBEVBackbone / BaseBEVBackboneV1
+ * Dense 2-D BEV backbone (csrc/conv2d.hip): the layers of BaseBEVBackbone / BaseBEVBackboneV1 and of PillarRes18BackBone8x's dense conv5
  * ===================================================================================== */
 
 /* Semantics (torch.nn.Conv2d / ConvTranspose2d / eval BatchNorm2d / ReLU as pcdet/models/backbones_2d/base_bev_backbone.py:6-204 stacks them).
@@ -610,7 +613,7 @@ int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nb
  *             per axis), or kernel = stride = s in {1, 2, 4}, padding 0 (output floor(H / s)).  lvq_conv2d_out_size is that rule.
  *   deconv    ConvTranspose2d(kernel = stride = s), s in {1, 2, 4}, weight torch's [C_in, C_out, s, s]:
  *             out[b, co, s y + i, s x + j] = sum_ci in[b, ci, y, x] W[ci, co, i, j]  (a GEMM with s^2 C_out columns + a pixel shuffle).
- *   epilogue  y = [relu](acc * scale[co] + shift[co]); scale / shift both or neither (NULL = identity).
+ *   epilogue  y = [relu](acc * scale[co] + shift[co]); scale / shift both or neither (NULL = identity).  lvq_conv2d_res adds a residual.
  *   outputs   out_hi (+ out_lo) planes [B, OH, OW, out_c_total] and / or out_f32 [B, out_c_total, OH, OW] fp32 (the reference's
  *             `spatial_features_2d` layout); at least one.  The layer writes channels out_c_off .. out_c_off + c_out - 1 of either and
  *             nothing else: deblocks write straight into their range of the concatenated result.
@@ -625,7 +628,13 @@ int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nb
  *   lvq_conv2d_out_size        output size of one axis, or the negative error code                                     (host only)
  *   lvq_conv2d_packed_elems    (c_in rounded up to 32) * kernel^2 * c_out bf16 elements per part, 0 outside the family (host only;
  *                              transposed != 0: kernel is the stride s of the transposed conv)
- *   lvq_conv2d_pack_weights    once per weights version: fp32 weight -> w_hi (+ w_lo, or NULL) in MFMA-fragment order */
+ *   lvq_conv2d_pack_weights    once per weights version: fp32 weight -> w_hi (+ w_lo, or NULL) in MFMA-fragment order
+ *   lvq_conv2d_res             lvq_conv2d with a residual operand (the dense BasicBlock of spconv_backbone_2d.py:79-111): res_hi (+ res_lo)
+ *                              are planes [B, OH, OW, c_out], the layout of this layer's own output planes without a channel offset, and
+ *                              y = [relu](acc * scale + shift + res), res = hi + lo in the bf16x3 form (res_lo may be NULL = hi alone), res =
+ *                              hi in the plain form.  A conv bias is folded by the caller: shift' = bias * scale + shift.  res_hi == NULL,
+ *                              res_lo in the plain form (w_lo == NULL) and planes that are not 16-byte aligned follow the rules above
+ *                              (LVQ_EINVAL / LVQ_EINVAL / LVQ_EUNSUPPORTED), before any launch. */
 size_t lvq_conv2d_plane_elems(int batch, int c, int h, int w);
 int lvq_conv2d_out_size(int in, int kernel, int stride);
 int lvq_conv2d_to_planes(const float *x, int batch, int c, int h, int w, lvq_bf16 *hi, lvq_bf16 *lo, lvq_stream_t stream);
@@ -635,6 +644,9 @@ int lvq_conv2d_pack_weights(const float *weight, int c_out, int c_in, int kernel
 int lvq_conv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
                int c_out, int kernel, int stride, const float *scale, const float *shift, int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo,
                float *out_f32, int out_c_total, int out_c_off, lvq_stream_t stream);
+int lvq_conv2d_res(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
+                   int c_out, int kernel, int stride, const float *scale, const float *shift, const lvq_bf16 *res_hi, const lvq_bf16 *res_lo,
+                   int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo, float *out_f32, int out_c_total, int out_c_off, lvq_stream_t stream);
 int lvq_deconv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
                  int c_out, int stride, const float *scale, const float *shift, int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo, float *out_f32,
                  int out_c_total, int out_c_off, lvq_stream_t stream);

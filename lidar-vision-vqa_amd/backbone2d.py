@@ -61,14 +61,17 @@ def to_planes(x: torch.Tensor, split: bool) -> Planes:
 
 
 class _Layer:
-    """One conv / transposed conv + BatchNorm2d + ReLU of a block or deblock: reads the containers' tensors, never calls them."""
+    """One conv / transposed conv + BatchNorm2d + ReLU of a block or deblock: reads the containers' tensors, never calls them.
+    A conv bias (the dense BasicBlock of the pillar backbones has one) is folded into the shift: shift' = bias * scale + shift."""
 
     def __init__(self, conv: nn.Module, bn: Optional[nn.BatchNorm2d], relu: bool):
         self.conv, self.bn, self.relu = conv, bn, relu
         self.transposed = isinstance(conv, nn.ConvTranspose2d)
         k, s, p = conv.kernel_size, conv.stride, conv.padding
-        if k[0] != k[1] or s[0] != s[1] or p[0] != p[1] or conv.bias is not None or conv.groups != 1 or tuple(conv.dilation) != (1, 1):
-            raise NotImplementedError("dense 2-D convolutions: square kernels, no bias, dilation 1, groups 1")
+        if k[0] != k[1] or s[0] != s[1] or p[0] != p[1] or conv.groups != 1 or tuple(conv.dilation) != (1, 1):
+            raise NotImplementedError("dense 2-D convolutions: square kernels, dilation 1, groups 1")
+        if conv.bias is not None and (bn is None or self.transposed):
+            raise NotImplementedError("dense 2-D convolutions: a bias only in front of a BatchNorm2d (it is folded into the shift)")
         self.kernel, self.stride, self.padding = int(k[0]), int(s[0]), int(p[0])
         self.c_in, self.c_out = conv.in_channels, conv.out_channels
         self._cache = {}
@@ -93,12 +96,20 @@ class _Layer:
         bn = self.bn
         if bn is None:
             return None, None
-        return F.derived(self._cache, "bn", (bn.weight, bn.bias, bn.running_mean, bn.running_var), lambda: F.fold_batchnorm(bn), (bn.eps,))
+        bias = self.conv.bias
+
+        def build():
+            scale, shift = F.fold_batchnorm(bn)
+            if bias is not None:
+                shift = (bias.detach().float() * scale + shift).contiguous()
+            return scale, shift
+        return F.derived(self._cache, "bn", (bn.weight, bn.bias, bn.running_mean, bn.running_var, bias), build, (bn.eps,))
 
     def run(self, x: Planes, split: bool, pad: int = 0, planes: Optional[Planes] = None, f32: Optional[torch.Tensor] = None,
-            c_off: int = 0) -> Optional[Planes]:
+            c_off: int = 0, residual: Optional[Planes] = None) -> Optional[Planes]:
         """One launch.  The result goes to channels c_off .. c_off + c_out - 1 of `planes` (made here when neither target is given)
-        and / or of `f32` [B, C_total, OH, OW]."""
+        and / or of `f32` [B, C_total, OH, OW].  `residual` (planes of the output's own size and channels) is added before the ReLU:
+        lvq_conv2d_res."""
         if x.c != self.c_in:
             raise F.LvqError(f"{type(self.conv).__name__}: expected {self.c_in} input channels, got {x.c}")
         if not self.transposed and (self.kernel, self.padding + pad) not in ((3, 1), (self.stride, 0)):
@@ -119,7 +130,12 @@ class _Layer:
                c_off, F.stream_ptr(dev))
         head = (F.ptr(x.hi), F.ptr(x.lo), x.batch, x.h, x.w, self.c_in, F.ptr(hi), F.ptr(lo), self.c_out)
         tail = (F.ptr(scale), F.ptr(shift), int(self.relu))
-        if self.transposed:
+        if residual is not None:
+            if self.transposed or (residual.batch, residual.h, residual.w, residual.c) != (x.batch, oh, ow, self.c_out):
+                raise F.LvqError(f"{type(self.conv).__name__}: the residual must be [{x.batch}, {oh}, {ow}, {self.c_out}] planes of a conv")
+            F.check(_lib().lvq_conv2d_res(*head, self.kernel, self.stride, F.ptr(scale), F.ptr(shift), F.ptr(residual.hi),
+                                          F.ptr(residual.lo if split else None), int(self.relu), *out), "lvq_conv2d_res")
+        elif self.transposed:
             F.check(_lib().lvq_deconv2d(*head, self.stride, *tail, *out), "lvq_deconv2d")
         else:
             F.check(_lib().lvq_conv2d(*head, self.kernel, self.stride, *tail, *out), "lvq_conv2d")

@@ -1,15 +1,17 @@
-"""The sparse 3-D convolution backbone between MeanVFE and the BEV canvas: the reference's module API
-(pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225, spconv 2.x layers through pcdet/utils/spconv_utils.py)
-on the HIP kernels of csrc/sparse_conv.hip.  spconv itself is not a dependency.
+"""The sparse 3-D convolution backbones between MeanVFE and the BEV canvas: the reference's module API
+(pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225 and spconv_backbone.py:8-295, spconv 2.x layers through
+pcdet/utils/spconv_utils.py) on the HIP kernels of csrc/sparse_conv.hip.  spconv itself is not a dependency.
 
   SubMConv3d / SubMConv2d / SparseConv3d / SparseConv2d   parameter containers (weight [C_out, *kernel, C_in], optional bias) whose
                           forward is two C-ABI calls: lvq_sparse_conv_rules (once per indice_key: layers that share a key share the
                           neighbour table, as in spconv) and lvq_sparse_conv (gather-form implicit GEMM + fused epilogue)
   SparseSequential        runs its children; a conv followed by BatchNorm1d (and ReLU) becomes ONE kernel launch with the folded
                           eval-mode statistics in its epilogue
-  post_act_block, SparseBasicBlock, VoxelResBackBone8xVoxelNeXt   the reference's containers under the reference's names, so a
-                          checkpoint's `backbone_3d.*` entries load with strict=True
-  backbones_3d_all        registry with the reference's NAME string
+  post_act_block, SparseBasicBlock, VoxelResBackBone8xVoxelNeXt, VoxelBackBone8x, VoxelResBackBone8x   the reference's containers
+                          under the reference's names, so a checkpoint's `backbone_3d.*` entries load with strict=True.  The last two
+                          (SECOND / CenterPoint / TransFusion / BEVFusion) end in a (3, 1, 1) stride (2, 1, 1) conv whose 3-D result
+                          goes through bev.HeightCompression into backbone2d.BaseBEVBackbone.
+  backbones_3d_all        registry with the reference's NAME strings (backbone_pillar.py adds the two pillar backbones)
 
 Inference only: train() mode, or a call with gradients in reach, raises LvqError, and so do CPU tensors (no fallback).
 Precision: `precision` of the backbone, "bf16x3" (hi + lo operands, three MFMA passes: the default here, it meets the 1e-3 parity bar)
@@ -135,7 +137,7 @@ class _SparseConv(nn.Module):
         n = L.lvq_sparse_conv_packed_elems(self.out_channels, kvol, self.in_channels)
         if n == 0:
             raise F.LvqError(f"lvq_sparse_conv: channels ({self.in_channels} -> {self.out_channels}) outside the kernel family "
-                             "(C_in in 4, 5, 16, 32, 64, 128; C_out in 16, 32, 64, 128)")
+                             "(C_in in 4, 5, 16, 32, 64, 128 with C_out in 16, 32, 64, 128; or 128 -> 256, 256 -> 256)")
         w = self.weight.detach().float().contiguous()
         hi = torch.empty((n,), dtype=torch.int16, device=w.device)
         lo = torch.empty((n,), dtype=torch.int16, device=w.device) if split else None
@@ -261,13 +263,17 @@ def post_act_block(in_channels, out_channels, kernel_size, indice_key=None, stri
 class SparseBasicBlock(nn.Module):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride=1, norm_fn=None, downsample=None, indice_key=None):
+    conv_cls = SubMConv3d
+
+    def __init__(self, inplanes, planes, stride=1, bias=None, norm_fn=None, downsample=None, indice_key=None):
         super().__init__()
         assert norm_fn is not None
-        self.conv1 = SubMConv3d(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=True, indice_key=indice_key)
+        if bias is None:
+            bias = norm_fn is not None
+        self.conv1 = self.conv_cls(inplanes, planes, kernel_size=3, stride=stride, padding=1, bias=bias, indice_key=indice_key)
         self.bn1 = norm_fn(planes)
         self.relu = nn.ReLU()
-        self.conv2 = SubMConv3d(planes, planes, kernel_size=3, stride=stride, padding=1, bias=True, indice_key=indice_key)
+        self.conv2 = self.conv_cls(planes, planes, kernel_size=3, stride=stride, padding=1, bias=bias, indice_key=indice_key)
         self.bn2 = norm_fn(planes)
         self.downsample = downsample
         self.stride = stride
@@ -349,4 +355,85 @@ class VoxelResBackBone8xVoxelNeXt(nn.Module):
         return batch_dict
 
 
-backbones_3d_all = {"VoxelResBackBone8xVoxelNeXt": VoxelResBackBone8xVoxelNeXt}
+def _cfg_get(model_cfg, key, default=None):
+    """model_cfg.get(key, default) for the reference's EasyDict, a dict, or no config at all."""
+    return model_cfg.get(key, default) if model_cfg is not None and hasattr(model_cfg, "get") else default
+
+
+class _VoxelBackBone8x(nn.Module):
+    """What spconv_backbone.py's two backbones share: the constructor's bookkeeping and the forward."""
+
+    def __init__(self, model_cfg, input_channels, grid_size, **kwargs):
+        super().__init__()
+        self.model_cfg = model_cfg
+        g = [int(v) for v in grid_size]
+        self.sparse_shape = [g[2] + 1, g[1], g[0]]    # grid_size[::-1] + [1, 0, 0]
+        self.precision: Optional[str] = None          # None -> "bf16x3"
+        self.num_point_features = 128
+
+    def _conv_out(self, c_in, norm_fn):
+        last_pad = _cfg_get(self.model_cfg, "last_pad", 0)
+        return SparseSequential(SparseConv3d(c_in, 128, (3, 1, 1), stride=(2, 1, 1), padding=last_pad, bias=False, indice_key="spconv_down2"),
+                                norm_fn(128), nn.ReLU())
+
+    def forward(self, batch_dict):
+        name = type(self).__name__
+        if AG.wanted(self, batch_dict["voxel_features"]):
+            raise F.LvqError(f"{name}: inference-only kernels (BatchNorm folded); call it in eval() mode under torch.no_grad()")
+        feats, coords = batch_dict["voxel_features"], batch_dict["voxel_coords"]
+        F.require_cuda(feats, coords)
+        x = SparseConvTensor(feats.float().contiguous(), coords.to(torch.int32).contiguous(), self.sparse_shape, batch_dict["batch_size"],
+                             None, self.precision or DEFAULT_MODE)
+        x = self.conv_input(x)
+        x_conv1 = self.conv1(x)
+        x_conv2 = self.conv2(x_conv1)
+        x_conv3 = self.conv3(x_conv2)
+        x_conv4 = self.conv4(x_conv3)
+        out = self.conv_out(x_conv4)                   # [D4, H, W] -> [(D4 - 3) // 2 + 1, H, W]: HeightCompression folds z into the channels
+        batch_dict.update({"encoded_spconv_tensor": out, "encoded_spconv_tensor_stride": 8})
+        batch_dict.update({"multi_scale_3d_features": {"x_conv1": x_conv1, "x_conv2": x_conv2, "x_conv3": x_conv3, "x_conv4": x_conv4}})
+        batch_dict.update({"multi_scale_3d_strides": {"x_conv1": 1, "x_conv2": 2, "x_conv3": 4, "x_conv4": 8}})
+        return batch_dict
+
+
+class VoxelBackBone8x(_VoxelBackBone8x):
+    def __init__(self, model_cfg, input_channels, grid_size, **kwargs):
+        super().__init__(model_cfg, input_channels, grid_size, **kwargs)
+        norm_fn = partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01)
+        block = partial(post_act_block, norm_fn=norm_fn)
+        self.conv_input = SparseSequential(SubMConv3d(input_channels, 16, 3, padding=1, bias=False, indice_key="subm1"), norm_fn(16), nn.ReLU())
+        self.conv1 = SparseSequential(block(16, 16, 3, padding=1, indice_key="subm1"))
+        self.conv2 = SparseSequential(block(16, 32, 3, stride=2, padding=1, indice_key="spconv2", conv_type="spconv"),
+                                      block(32, 32, 3, padding=1, indice_key="subm2"), block(32, 32, 3, padding=1, indice_key="subm2"))
+        self.conv3 = SparseSequential(block(32, 64, 3, stride=2, padding=1, indice_key="spconv3", conv_type="spconv"),
+                                      block(64, 64, 3, padding=1, indice_key="subm3"), block(64, 64, 3, padding=1, indice_key="subm3"))
+        self.conv4 = SparseSequential(block(64, 64, 3, stride=2, padding=(0, 1, 1), indice_key="spconv4", conv_type="spconv"),
+                                      block(64, 64, 3, padding=1, indice_key="subm4"), block(64, 64, 3, padding=1, indice_key="subm4"))
+        self.conv_out = self._conv_out(64, norm_fn)
+        self.backbone_channels = {"x_conv1": 16, "x_conv2": 32, "x_conv3": 64, "x_conv4": 64}
+
+
+class VoxelResBackBone8x(_VoxelBackBone8x):
+    def __init__(self, model_cfg, input_channels, grid_size, **kwargs):
+        super().__init__(model_cfg, input_channels, grid_size, **kwargs)
+        use_bias = _cfg_get(model_cfg, "USE_BIAS", None)
+        norm_fn = partial(nn.BatchNorm1d, eps=1e-3, momentum=0.01)
+        block = partial(post_act_block, norm_fn=norm_fn)
+        res = partial(SparseBasicBlock, bias=use_bias, norm_fn=norm_fn)
+        self.conv_input = SparseSequential(SubMConv3d(input_channels, 16, 3, padding=1, bias=False, indice_key="subm1"), norm_fn(16), nn.ReLU())
+        self.conv1 = SparseSequential(res(16, 16, indice_key="res1"), res(16, 16, indice_key="res1"))
+        self.conv2 = SparseSequential(block(16, 32, 3, stride=2, padding=1, indice_key="spconv2", conv_type="spconv"),
+                                      res(32, 32, indice_key="res2"), res(32, 32, indice_key="res2"))
+        self.conv3 = SparseSequential(block(32, 64, 3, stride=2, padding=1, indice_key="spconv3", conv_type="spconv"),
+                                      res(64, 64, indice_key="res3"), res(64, 64, indice_key="res3"))
+        self.conv4 = SparseSequential(block(64, 128, 3, stride=2, padding=(0, 1, 1), indice_key="spconv4", conv_type="spconv"),
+                                      res(128, 128, indice_key="res4"), res(128, 128, indice_key="res4"))
+        self.conv_out = self._conv_out(128, norm_fn)
+        self.backbone_channels = {"x_conv1": 16, "x_conv2": 32, "x_conv3": 64, "x_conv4": 128}
+
+
+backbones_3d_all = {"VoxelResBackBone8xVoxelNeXt": VoxelResBackBone8xVoxelNeXt, "VoxelBackBone8x": VoxelBackBone8x,
+                    "VoxelResBackBone8x": VoxelResBackBone8x}
+
+# the pillar backbones (spconv_backbone_2d.py) live in backbone_pillar.py, which builds on this module: their entries are added from that side
+from . import backbone_pillar as _backbone_pillar  # noqa: E402,F401

@@ -13,6 +13,9 @@
 //                            pixels.  The transposed conv is the 1 x 1 case with N = s^2 C_out columns and a pixel-shuffle epilogue.
 //                            Epilogue [relu](acc * scale + shift) from the accumulators into operand planes and / or fp32 [B, C, H, W], both
 //                            with a channel offset inside a wider buffer (the concat is never a copy).
+//   lvq_conv2d_res           the same kernel body with residual planes [B, OH, OW, c_out] in the epilogue, [relu](acc * scale + shift + res):
+//                            the dense BasicBlock of PillarRes18BackBone8x (spconv_backbone_2d.py:79-111).  Its own argument record, so the
+//                            arguments and registers of the plain instantiations do not move.
 //   order                    channel chunks ascending, taps ascending inside a chunk, 32-channel steps ascending inside a tap, hi*hi + hi*lo +
 //                            lo*hi; no atomics.  A pixel's bits depend on its receptive field only.
 #include "common.h"
@@ -43,6 +46,11 @@ struct ConvArgs {
     int n_total, c_out, ups;      // GEMM columns = ups^2 * c_out
     int c_total, c_off, relu;
     int tiles_x;
+    static constexpr bool RES = false;
+};
+struct ConvResArgs : ConvArgs {
+    const uint16_t *res_hi, *res_lo;              // [B, OH, OW, c_out]; res_lo may be NULL
+    static constexpr bool RES = true;
 };
 
 __global__ void __launch_bounds__(256) k_to_planes(const float *__restrict__ x, int c, int64_t hw, int cp, uint16_t *__restrict__ hi,
@@ -98,8 +106,10 @@ __global__ void __launch_bounds__(256) k_pack_w2d(const float *__restrict__ w, i
     if (lo) lo[t] = f32_to_bf16(v - bf16_to_f32(h));
 }
 
-template <int K, int S, int CK, bool SPLIT>
-__global__ void __launch_bounds__(256) k_conv2d(const ConvArgs a) {
+// A = ConvArgs, or ConvResArgs: the residual planes [B, OH, OW, c_out] join the epilogue (ups = 1 only).  The residual form has an argument
+// record of its own, so ConvArgs -- and with it every register of the plain instantiations -- stays as it is.
+template <int K, int S, int CK, bool SPLIT, typename A = ConvArgs>
+__global__ void __launch_bounds__(256) k_conv2d(const A a) {
     constexpr bool HALO = K == 3;
     constexpr int TAPS = K * K, KS = CK / 32, PITCH = CK + 8;           // bf16 elements; rows stay 16-byte aligned
     constexpr int RH = HALO ? (TH - 1) * S + K : TH, RW = HALO ? (TW - 1) * S + K : TW;      // the staged region, in pixels
@@ -198,6 +208,12 @@ __global__ void __launch_bounds__(256) k_conv2d(const ConvArgs a) {
                 if (oy >= a.oh || ox >= a.ow) continue;
                 float v = acc[mt][nt][j];
                 if (a.scale) v = v * sc + sh;
+                if constexpr (A::RES) {
+                    const int64_t r = (((int64_t)b * a.oh + oy) * a.ow + ox) * a.c_out + co;
+                    float res = bf16_to_f32(a.res_hi[r]);
+                    if (a.res_lo) res += bf16_to_f32(a.res_lo[r]);
+                    v += res;
+                }
                 if (a.relu) v = v > 0.f ? v : 0.f;
                 const int y = oy * a.ups + si, x = ox * a.ups + sj;
                 if (a.out_hi) {
@@ -212,23 +228,32 @@ __global__ void __launch_bounds__(256) k_conv2d(const ConvArgs a) {
     }
 }
 
-template <int K, int S, int CK> void launch_split(bool split, dim3 grid, hipStream_t st, const ConvArgs &a) {
-    if (split)
+template <int K, int S, int CK>
+void launch_split(bool split, dim3 grid, hipStream_t st, const ConvArgs &a, const lvq_bf16 *res_hi, const lvq_bf16 *res_lo) {
+    if (res_hi) {
+        ConvResArgs ra;
+        static_cast<ConvArgs &>(ra) = a;
+        ra.res_hi = res_hi; ra.res_lo = res_lo;
+        if (split)
+            hipLaunchKernelGGL((k_conv2d<K, S, CK, true, ConvResArgs>), grid, dim3(256), 0, st, ra);
+        else
+            hipLaunchKernelGGL((k_conv2d<K, S, CK, false, ConvResArgs>), grid, dim3(256), 0, st, ra);
+    } else if (split)
         hipLaunchKernelGGL((k_conv2d<K, S, CK, true>), grid, dim3(256), 0, st, a);
     else
         hipLaunchKernelGGL((k_conv2d<K, S, CK, false>), grid, dim3(256), 0, st, a);
 }
 
-// the shared body of lvq_conv2d (ups = 1) and lvq_deconv2d (kernel = stride = 1 on the canvas, ups = s)
+// the shared body of lvq_conv2d, lvq_conv2d_res (ups = 1; res_hi != NULL) and lvq_deconv2d (kernel = stride = 1 on the canvas, ups = s)
 int run_conv(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo, int c_out,
              int kernel, int stride, int ups, const float *scale, const float *shift, int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo, float *out_f32,
-             int out_c_total, int out_c_off, lvq_stream_t stream) {
+             int out_c_total, int out_c_off, lvq_stream_t stream, const lvq_bf16 *res_hi = nullptr, const lvq_bf16 *res_lo = nullptr) {
     if (batch <= 0 || h <= 0 || w <= 0 || c_in <= 0 || c_out <= 0 || kernel <= 0 || stride <= 0) return LVQ_EINVAL;
     if ((scale == nullptr) != (shift == nullptr) || (in_lo == nullptr) != (w_lo == nullptr)) return LVQ_EINVAL;
     if (!in_hi || !w_hi || (!out_hi && !out_f32) || (out_lo && !out_hi)) return LVQ_EINVAL;
     if (out_c_off < 0 || out_c_total <= 0 || (int64_t)out_c_off + c_out > out_c_total) return LVQ_EINVAL;
     if (!cin_ok(c_in) || !cout_ok(c_out) || !geom_ok(kernel, stride) || batch > 65535) return LVQ_EUNSUPPORTED;
-    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)w_hi | (uintptr_t)w_lo) & 15) return LVQ_EUNSUPPORTED;
+    if (((uintptr_t)in_hi | (uintptr_t)in_lo | (uintptr_t)w_hi | (uintptr_t)w_lo | (uintptr_t)res_hi | (uintptr_t)res_lo) & 15) return LVQ_EUNSUPPORTED;
     ConvArgs a;
     a.in_hi = in_hi; a.in_lo = in_lo; a.w_hi = w_hi; a.w_lo = w_lo; a.scale = scale; a.shift = shift;
     a.out_hi = out_hi; a.out_lo = out_lo; a.out_f32 = out_f32;
@@ -243,11 +268,11 @@ int run_conv(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int
     const dim3 grid((unsigned)tiles, (unsigned)(a.n_total / BN), (unsigned)batch);
     hipStream_t st = lvq_s(stream);
     const bool split = w_lo != nullptr, wide = a.cp % 64 == 0;
-    if (kernel == 3 && stride == 1) { if (wide) launch_split<3, 1, 64>(split, grid, st, a); else launch_split<3, 1, 32>(split, grid, st, a); }
-    else if (kernel == 3) launch_split<3, 2, 32>(split, grid, st, a);
-    else if (kernel == 1) { if (wide) launch_split<1, 1, 64>(split, grid, st, a); else launch_split<1, 1, 32>(split, grid, st, a); }
-    else if (kernel == 2) { if (wide) launch_split<2, 2, 64>(split, grid, st, a); else launch_split<2, 2, 32>(split, grid, st, a); }
-    else { if (wide) launch_split<4, 4, 64>(split, grid, st, a); else launch_split<4, 4, 32>(split, grid, st, a); }
+    if (kernel == 3 && stride == 1) { if (wide) launch_split<3, 1, 64>(split, grid, st, a, res_hi, res_lo); else launch_split<3, 1, 32>(split, grid, st, a, res_hi, res_lo); }
+    else if (kernel == 3) launch_split<3, 2, 32>(split, grid, st, a, res_hi, res_lo);
+    else if (kernel == 1) { if (wide) launch_split<1, 1, 64>(split, grid, st, a, res_hi, res_lo); else launch_split<1, 1, 32>(split, grid, st, a, res_hi, res_lo); }
+    else if (kernel == 2) { if (wide) launch_split<2, 2, 64>(split, grid, st, a, res_hi, res_lo); else launch_split<2, 2, 32>(split, grid, st, a, res_hi, res_lo); }
+    else { if (wide) launch_split<4, 4, 64>(split, grid, st, a, res_hi, res_lo); else launch_split<4, 4, 32>(split, grid, st, a, res_hi, res_lo); }
     return lvq_launch_status();
 }
 
@@ -297,6 +322,14 @@ extern "C" int lvq_conv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batc
                           float *out_f32, int out_c_total, int out_c_off, lvq_stream_t stream) {
     return run_conv(in_hi, in_lo, batch, h, w, c_in, w_hi, w_lo, c_out, kernel, stride, 1, scale, shift, relu, out_hi, out_lo, out_f32, out_c_total,
                     out_c_off, stream);
+}
+
+extern "C" int lvq_conv2d_res(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,
+                              int c_out, int kernel, int stride, const float *scale, const float *shift, const lvq_bf16 *res_hi, const lvq_bf16 *res_lo,
+                              int relu, lvq_bf16 *out_hi, lvq_bf16 *out_lo, float *out_f32, int out_c_total, int out_c_off, lvq_stream_t stream) {
+    if (!res_hi || (res_lo && !w_lo)) return LVQ_EINVAL;                // no residual at all, or a lo plane in the plain form
+    return run_conv(in_hi, in_lo, batch, h, w, c_in, w_hi, w_lo, c_out, kernel, stride, 1, scale, shift, relu, out_hi, out_lo, out_f32, out_c_total,
+                    out_c_off, stream, res_hi, res_lo);
 }
 
 extern "C" int lvq_deconv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h, int w, int c_in, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo,

@@ -1,5 +1,6 @@
-// csrc/sparse_conv.hip -- the sparse convolutions of VoxelResBackBone8xVoxelNeXt (spconv 2.x SubMConv3d / SparseConv3d / SparseConv2d /
-// SubMConv2d as pcdet/models/backbones_3d/spconv_backbone_voxelnext.py:8-225 uses them), gfx950.
+// csrc/sparse_conv.hip -- the sparse convolutions of VoxelResBackBone8xVoxelNeXt, VoxelBackBone8x / VoxelResBackBone8x and PillarBackBone8x /
+// PillarRes18BackBone8x (spconv 2.x SubMConv3d / SparseConv3d / SparseConv2d / SubMConv2d as pcdet/models/backbones_3d/
+// spconv_backbone_voxelnext.py:8-225, spconv_backbone.py:8-295 and spconv_backbone_2d.py:8-300 use them), gfx950.
 //
 //   lvq_sparse_conv_rules   the active output set and the neighbour table nbr [n_out, K] (input row per kernel offset, -1 = absent).
 //                           No hash table and no sort: the ascending-unique machinery of the dynamic voxeliser (voxel.hip /
@@ -19,6 +20,8 @@
 //                           epilogue is applied from the accumulators.  An offset no row of the tile has is skipped (a row without it
 //                           adds exact zeros, so skipping changes no bit): a row's result depends on its own neighbours only.
 //                           C_in of 4 / 5 / 16 is zero-padded to the MFMA depth of 32 in LDS and in the packed weights.
+//                           C_out = 256 (C_in 128 or 256): a wave owns 64 columns; C_in = 256 runs as two 128-channel stages per offset,
+//                           ascending, each with its own gather and its own weight fragments, so LDS stays that of the 128-channel tile.
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -172,16 +175,22 @@ __global__ void __launch_bounds__(256) k_pack_w(const float *__restrict__ w, int
 
 constexpr int TILE_M = 64;
 
+// (C_out = 256 asks for two waves per SIMD: left alone the hi + lo form takes 200 VGPRs + 64 AGPRs, eight over what two workgroups per CU
+// allow, and one workgroup per CU has nobody to hide its gather behind; the narrower instantiations keep the compiler's own choice)
 template <int CIN_PAD, int COUT, bool SPLIT>
-__global__ void __launch_bounds__(256) k_sparse_conv(const float *__restrict__ feat, int64_t n_in, int c_in, const int32_t *__restrict__ nbr, int kvol,
-                                                     int64_t n_cap, const int32_t *__restrict__ n_out_dev, const lvq_bf16 *__restrict__ w_hi,
-                                                     const lvq_bf16 *__restrict__ w_lo, const float *__restrict__ bias, const float *__restrict__ scale,
-                                                     const float *__restrict__ shift, const float *__restrict__ residual, int relu, float *__restrict__ out) {
-    constexpr int PITCH = CIN_PAD + 8;                      // bf16 elements; rows stay 16-byte aligned
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(COUT == 256 ? 2 : 1)))
+k_sparse_conv(const float *__restrict__ feat, int64_t n_in, int c_in, const int32_t *__restrict__ nbr, int kvol, int64_t n_cap,
+              const int32_t *__restrict__ n_out_dev, const lvq_bf16 *__restrict__ w_hi, const lvq_bf16 *__restrict__ w_lo,
+              const float *__restrict__ bias, const float *__restrict__ scale, const float *__restrict__ shift,
+              const float *__restrict__ residual, int relu, float *__restrict__ out) {
+    // K runs in stages of CK channels (one stage up to 128 channels, two for 256): the LDS tile and the weight fragments a wave holds are
+    // those of one stage, so C_in = 256 costs no more LDS or registers per column than 128 does
+    constexpr int CK = CIN_PAD < 128 ? CIN_PAD : 128, NCH = CIN_PAD / CK;
+    constexpr int PITCH = CK + 8;                           // bf16 elements; rows stay 16-byte aligned
     // the four waves as WM x WN: a wave owns MT 16-row tiles x NT 16-column tiles, so a W_o fragment is read once per workgroup (by the
     // one wave that owns its columns) when C_out >= 64, and the LDS rows are read by WN waves
     constexpr int WN = COUT / 16 < 4 ? COUT / 16 : 4, WM = 4 / WN;
-    constexpr int MT = TILE_M / 16 / WM, NT = COUT / 16 / WN, KS = CIN_PAD / 32;
+    constexpr int MT = TILE_M / 16 / WM, NT = COUT / 16 / WN, KS = CK / 32;
     __shared__ __attribute__((aligned(16))) uint16_t a_hi[TILE_M * PITCH];
     __shared__ __attribute__((aligned(16))) uint16_t a_lo[SPLIT ? TILE_M * PITCH : 8];
     __shared__ int s_nb2[2][TILE_M];                        // by offset parity: wave 0 may post the next offset while others still read this one
@@ -213,64 +222,68 @@ __global__ void __launch_bounds__(256) k_sparse_conv(const float *__restrict__ f
         }
         if (tid < TILE_M) s_nb[tid] = r;
         if (!__syncthreads_or(r >= 0)) continue;            // no row of the tile has this offset (uniform; also fences the LDS tile)
-        // this wave's W_o fragments (16 bytes per lane each): issued before the gather, whose latency they share
-        bf16x8 bh[KS][NT], bl[KS][NT];
-        {
-            const int64_t wofs = ((int64_t)o * COUT + col0 + l15) * CIN_PAD + 8 * lq;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
+        for (int kc = 0; kc < NCH; ++kc) {
+            if (kc) __syncthreads();                            // the previous stage's LDS tile has been read
+            // this wave's W_o fragments of the stage (16 bytes per lane each): issued before the gather, whose latency they share
+            bf16x8 bh[KS][NT], bl[KS][NT];
+            {
+                const int64_t wofs = ((int64_t)o * COUT + col0 + l15) * CIN_PAD + kc * CK + 8 * lq;
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    bh[ks][nt] = *reinterpret_cast<const bf16x8 *>(w_hi + wofs + (int64_t)nt * 16 * CIN_PAD + ks * 32);
-                    bl[ks][nt] = SPLIT ? *reinterpret_cast<const bf16x8 *>(w_lo + wofs + (int64_t)nt * 16 * CIN_PAD + ks * 32) : bh[ks][nt];
-                }
-        }
-        // gather: four channels per thread and step, a row's channels on consecutive lanes
-        constexpr int QPR = CIN_PAD / 4;
+                for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-        for (int e0 = 0; e0 < TILE_M * QPR; e0 += 256) {
-            const int e = e0 + tid;
-            const int row = e / QPR, c4 = (e % QPR) * 4;
-            const int src = s_nb[row];
-            float v[4] = {0.f, 0.f, 0.f, 0.f};
-            if (src >= 0 && c4 < c_in) {
-                const float *p = feat + (int64_t)src * c_in + c4;
-                if ((c_in & 3) == 0) {
-                    const float4 f = *reinterpret_cast<const float4 *>(p);
-                    v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) v[j] = c4 + j < c_in ? p[j] : 0.f;
-                }
+                    for (int nt = 0; nt < NT; ++nt) {
+                        bh[ks][nt] = *reinterpret_cast<const bf16x8 *>(w_hi + wofs + (int64_t)nt * 16 * CIN_PAD + ks * 32);
+                        bl[ks][nt] = SPLIT ? *reinterpret_cast<const bf16x8 *>(w_lo + wofs + (int64_t)nt * 16 * CIN_PAD + ks * 32) : bh[ks][nt];
+                    }
             }
-            uint16_t h[4], l[4];
+            // gather: four channels per thread and step, a row's channels on consecutive lanes
+            constexpr int QPR = CK / 4;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                h[j] = f32_to_bf16(v[j]);
-                l[j] = SPLIT ? f32_to_bf16(v[j] - bf16_to_f32(h[j])) : (uint16_t)0;
+            for (int e0 = 0; e0 < TILE_M * QPR; e0 += 256) {
+                const int e = e0 + tid;
+                const int row = e / QPR, c4 = (e % QPR) * 4, cg = kc * CK + c4;      // c4: column of the LDS stage, cg: channel of the row
+                const int src = s_nb[row];
+                float v[4] = {0.f, 0.f, 0.f, 0.f};
+                if (src >= 0 && cg < c_in) {
+                    const float *p = feat + (int64_t)src * c_in + cg;
+                    if ((c_in & 3) == 0) {
+                        const float4 f = *reinterpret_cast<const float4 *>(p);
+                        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) v[j] = cg + j < c_in ? p[j] : 0.f;
+                    }
+                }
+                uint16_t h[4], l[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    h[j] = f32_to_bf16(v[j]);
+                    l[j] = SPLIT ? f32_to_bf16(v[j] - bf16_to_f32(h[j])) : (uint16_t)0;
+                }
+                *reinterpret_cast<uint2 *>(&a_hi[row * PITCH + c4]) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
+                if (SPLIT)
+                    *reinterpret_cast<uint2 *>(&a_lo[row * PITCH + c4]) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
             }
-            *reinterpret_cast<uint2 *>(&a_hi[row * PITCH + c4]) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
-            if (SPLIT)
-                *reinterpret_cast<uint2 *>(&a_lo[row * PITCH + c4]) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
-        }
-        __syncthreads();
+            __syncthreads();
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            // a 16-row tile none of whose rows has the offset is skipped (its LDS rows are zeros)
-            const bool mine = s_nb[row0 + mt * 16 + l15] >= 0;
-            if (__ballot(mine) == 0ull) continue;
-            const int arow = (row0 + mt * 16 + l15) * PITCH + 8 * lq;
+            for (int mt = 0; mt < MT; ++mt) {
+                // a 16-row tile none of whose rows has the offset is skipped (its LDS rows are zeros)
+                const bool mine = s_nb[row0 + mt * 16 + l15] >= 0;
+                if (__ballot(mine) == 0ull) continue;
+                const int arow = (row0 + mt * 16 + l15) * PITCH + 8 * lq;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&a_hi[arow + ks * 32]);
-                bf16x8 al = ah;
-                if (SPLIT) al = *reinterpret_cast<const bf16x8 *>(&a_lo[arow + ks * 32]);
+                for (int ks = 0; ks < KS; ++ks) {
+                    const bf16x8 ah = *reinterpret_cast<const bf16x8 *>(&a_hi[arow + ks * 32]);
+                    bf16x8 al = ah;
+                    if (SPLIT) al = *reinterpret_cast<const bf16x8 *>(&a_lo[arow + ks * 32]);
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[ks][nt], acc[mt][nt], 0, 0, 0);
-                    if (SPLIT) {
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[ks][nt], acc[mt][nt], 0, 0, 0);
-                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[ks][nt], acc[mt][nt], 0, 0, 0);
+                    for (int nt = 0; nt < NT; ++nt) {
+                        acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bh[ks][nt], acc[mt][nt], 0, 0, 0);
+                        if (SPLIT) {
+                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, bl[ks][nt], acc[mt][nt], 0, 0, 0);
+                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bh[ks][nt], acc[mt][nt], 0, 0, 0);
+                        }
                     }
                 }
             }
@@ -303,6 +316,8 @@ __global__ void __launch_bounds__(256) k_sparse_conv(const float *__restrict__ f
 int cin_pad_of(int c_in) { return c_in <= 32 ? 32 : c_in; }
 bool cin_ok(int c) { return c == 4 || c == 5 || c == 16 || c == 32 || c == 64 || c == 128; }
 bool cout_ok(int c) { return c == 16 || c == 32 || c == 64 || c == 128; }
+// the family: the narrow pairs above, plus the wide layers (128 -> 256) and (256 -> 256); C_in = 256 goes with C_out = 256 only
+bool pair_ok(int c_in, int c_out) { return c_out == 256 ? (c_in == 128 || c_in == 256) : (cin_ok(c_in) && cout_ok(c_out)); }
 
 struct RulesWs {
     float4 *pts;
@@ -337,7 +352,7 @@ int rules_geom(int ndim, const int32_t *shape, int batch, const int32_t *kernel,
             g.p[a] = g.k[a] / 2; g.out[a] = g.in[a];
         } else {
             g.s[a] = stride[j]; g.p[a] = padding[j];
-            if (g.s[a] <= 0 || g.p[a] < 0 || g.p[a] >= g.k[a]) return LVQ_EINVAL;
+            if (g.s[a] <= 0 || g.p[a] < 0) return LVQ_EINVAL;         // (p >= k is legal: conv_out with last_pad = 1 pads its 1-wide axes)
             const int num = g.in[a] + 2 * g.p[a] - g.k[a];
             if (num < 0) return LVQ_EINVAL;
             g.out[a] = num / g.s[a] + 1;
@@ -423,7 +438,7 @@ extern "C" int lvq_sparse_conv_rules(const int32_t *indices, int64_t n_in, int n
 }
 
 extern "C" size_t lvq_sparse_conv_packed_elems(int c_out, int k_vol, int c_in) {
-    if (!cin_ok(c_in) || !cout_ok(c_out) || k_vol <= 0 || k_vol > MAXK) return 0;
+    if (!pair_ok(c_in, c_out) || k_vol <= 0 || k_vol > MAXK) return 0;
     return (size_t)k_vol * c_out * cin_pad_of(c_in);
 }
 
@@ -446,7 +461,12 @@ template <int CIN_PAD, bool SPLIT, typename... Args> int launch_cout(int c_out, 
     }
     return lvq_launch_status();
 }
+template <int CIN_PAD, bool SPLIT, typename... Args> int launch_wide(unsigned nb, hipStream_t st, Args... args) {
+    hipLaunchKernelGGL((k_sparse_conv<CIN_PAD, 256, SPLIT>), dim3(nb), dim3(256), 0, st, args...);
+    return lvq_launch_status();
+}
 template <bool SPLIT, typename... Args> int launch_cin(int cin_pad, int c_out, unsigned nb, hipStream_t st, Args... args) {
+    if (c_out == 256) return cin_pad == 256 ? launch_wide<256, SPLIT>(nb, st, args...) : launch_wide<128, SPLIT>(nb, st, args...);
     switch (cin_pad) {
     case 32: return launch_cout<32, SPLIT>(c_out, nb, st, args...);
     case 64: return launch_cout<64, SPLIT>(c_out, nb, st, args...);
@@ -460,7 +480,7 @@ extern "C" int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const 
                                const lvq_bf16 *w_hi, const lvq_bf16 *w_lo, int c_out, const float *bias, const float *scale, const float *shift,
                                const float *residual, int relu, float *out, lvq_stream_t stream) {
     if (n_in < 0 || n_out_cap < 0 || c_in <= 0 || c_out <= 0 || k_vol <= 0 || (scale == nullptr) != (shift == nullptr)) return LVQ_EINVAL;
-    if (!cin_ok(c_in) || !cout_ok(c_out) || k_vol > MAXK) return LVQ_EUNSUPPORTED;
+    if (!pair_ok(c_in, c_out) || k_vol > MAXK) return LVQ_EUNSUPPORTED;
     if (n_out_cap == 0) return LVQ_OK;
     if (!nbr || !w_hi || !out || (n_in > 0 && !feat)) return LVQ_EINVAL;
     if (n_in >= (1ll << 31) || lvq_cdiv(n_out_cap, TILE_M) >= (1ll << 31)) return LVQ_EUNSUPPORTED;
