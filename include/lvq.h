@@ -163,6 +163,19 @@ int lvq_voxelize_dynamic(const float *pts, int64_t n, int c, int batch_size, con
                          int32_t *pt_coords, int32_t *unq_key, int32_t *unq_cnt, int32_t *coords_bzyx,
                          int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
+/* lvq_voxel_slab_plan (host only, a hook for tests): how the slab-binned kernels (csrc/voxel_binned.hip) would cut a key space --
+ * the ranking step behind lvq_voxelize_dynamic (dynamic_mean_vfe.py:53-72), lvq_voxelize_hard with voxel_path 1,
+ * lvq_sparse_conv_rules and lvq_sparse_bev_merge.  Slab s holds the keys [s << *logslab, (s + 1) << *logslab); one workgroup ranks it.
+ *   keyspace   batch * grid cells (the dynamic entry's key space: 2-D or 3-D; the rule builder's: batch * output cells)
+ *   n          points, or candidate cells (lvq_sparse_conv_rules: n_in * prod(ceil(k / s)); n_in for submanifold layers)
+ *   hard       0: the dynamic kernels (slabs up to 2^18 keys), 1: the hard kernels (up to 2^17)
+ *   caps       HOST int[4], the constants the slab kernels branch on: [0] voxels of a slab whose counters the dynamic write kernel
+ *              keeps in LDS, [1] voxels and [2] points of a slab whose state the hard slab kernel keeps in LDS (more: global
+ *              stand-ins), [3] points up to which a slab takes the hard path's brute-force kernel
+ * Launches nothing and touches no device memory.  NULL output, keyspace <= 0, n < 0 or hard outside {0, 1}: LVQ_EINVAL; a key space of
+ * 2^31 or more: LVQ_EOVERFLOW; one the binned kernels do not take (the caller's next path runs): LVQ_EUNSUPPORTED. */
+int lvq_voxel_slab_plan(int64_t keyspace, int64_t n, int hard, int *logslab, int *nslabs, int *caps);
+
 /* torch_scatter.scatter_mean(points[:,col0:col0+nc], unq_inv) as used by DynamicMeanVFE
  * (dynamic_mean_vfe.py:64) and for points_mean in the PFN variants (dynamic_pillar_vfe.py:105).
  * sums [m_cap,nc] must be zero on entry; on exit out = sums / max(cnt,1) (out may alias sums). */

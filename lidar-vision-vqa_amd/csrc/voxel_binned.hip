@@ -313,7 +313,7 @@ __global__ void __launch_bounds__(DYN_NT) k_dyn_slab_write(BinCfg cfg, Geom g, c
 
 // slab size: average ~256-512 points per slab, dense bitmap <= 16 KB (logslab <= 17), at most MAX_SLABS slabs.  max_ls = 18 (dynamic path:
 // 32-KB bitmaps, key spaces up to 2^31 -- e.g. 32 scenes of the 0.1 m nuScenes grid -- instead of handing those to the bitmap kernels of voxel.hip)
-static bool choose_cfg(int64_t keyspace, int64_t n, BinCfg &cfg, int max_ls = 17) {
+static bool choose_cfg(int64_t keyspace, int64_t n, BinCfg &cfg, int max_ls) {
     if (keyspace <= 0 || keyspace > ((int64_t)MAX_SLABS << max_ls) || keyspace >= (1ll << 31)) return false;
     int64_t want = n / 384 + 1;
     if (want > MAX_SLABS) want = MAX_SLABS;
@@ -564,7 +564,23 @@ __global__ void __launch_bounds__(256) k_hard_place(int n_sorted, BinCfg cfg, Ge
     }
 }
 
+// slab sizes of the two entries below: the dynamic path also takes 32-KB bitmaps (choose_cfg's comment)
+constexpr int DYN_MAX_LS = 18, HARD_MAX_LS = 17;
+
 }  // namespace vb
+
+// host-only query (include/lvq.h): the plan and the caps of the launches below, from the same choose_cfg and the same constants
+extern "C" int lvq_voxel_slab_plan(int64_t keyspace, int64_t n, int hard, int *logslab, int *nslabs, int *caps) {
+    using namespace vb;
+    if (keyspace <= 0 || n < 0 || (hard != 0 && hard != 1) || !logslab || !nslabs || !caps) return LVQ_EINVAL;
+    if (keyspace >= (1ll << 31)) return LVQ_EOVERFLOW;
+    BinCfg cfg;
+    if (!choose_cfg(keyspace, n, cfg, hard ? HARD_MAX_LS : DYN_MAX_LS)) return LVQ_EUNSUPPORTED;
+    *logslab = cfg.logslab;
+    *nslabs = cfg.nslabs;
+    caps[0] = DYN_VCAP; caps[1] = HARD_VCAP; caps[2] = HARD_PCAP; caps[3] = SMALL_PCAP;
+    return LVQ_OK;
+}
 
 // -------------------------------------------------------------------------------------------------
 // entry points used by voxel.hip's lvq_voxelize_dynamic (returns LVQ_EUNSUPPORTED when the binned path does not apply)
@@ -584,7 +600,7 @@ int lvq_binned_voxelize_dynamic(const float *pts, int64_t n, int c, int batch_si
     int64_t keyspace = (int64_t)batch_size * grid_host[0] * grid_host[1];
     if (ndim == 3) keyspace *= grid_host[2];
     BinCfg cfg;
-    if (!choose_cfg(keyspace, n, cfg, 18)) return LVQ_EUNSUPPORTED;
+    if (!choose_cfg(keyspace, n, cfg, DYN_MAX_LS)) return LVQ_EUNSUPPORTED;
     cfg.ndim = ndim; cfg.n_scenes = batch_size; cfg.mode = 0;
     LvqArena arena(ws, ws_bytes);
     DynBinWs w;
@@ -626,7 +642,7 @@ int lvq_binned_voxelize_hard(const float *pts, const int32_t *scene_off, int64_t
     if (c != 4 || (((uintptr_t)pts | (uintptr_t)voxels) & 15)) return LVQ_EUNSUPPORTED;
     const int64_t keyspace = (int64_t)n_scenes * grid_host[0] * grid_host[1] * grid_host[2];
     BinCfg cfg;
-    if (!choose_cfg(keyspace, n, cfg)) return LVQ_EUNSUPPORTED;
+    if (!choose_cfg(keyspace, n, cfg, HARD_MAX_LS)) return LVQ_EUNSUPPORTED;
     cfg.ndim = 3; cfg.n_scenes = n_scenes; cfg.mode = 1;
     LvqArena arena(ws, ws_bytes);
     HardBinWs w;

@@ -46,6 +46,35 @@ def test_host_only_entry_points(lib):
     assert lib.lvq_voxelize_dynamic_workspace_bytes(ctypes.c_int64(10), ctypes.c_int(64), g2, ctypes.c_int(3)) == 0
 
 
+def test_voxel_slab_plan_is_host_only_and_pinned(lib):
+    """lvq_voxel_slab_plan: what voxel_binned.hip's choose_cfg makes of a (key space, count) and the caps its slab kernels branch on.
+    The first three pairs are a pillar grid with ten full columns, a 1024 x 5 sheet of the 0.1 m grid and the candidates of a strided
+    2-D layer on a 4096 x 4096 input: sparse overall, so the slabs are large (tests/test_gpu_voxel_slab_routes.py fills one of them)."""
+    def plan(ks, n, hard, ls=True, ns=True, caps=True):
+        a, b, c = ctypes.c_int(-1), ctypes.c_int(-1), (ctypes.c_int * 4)(-1, -1, -1, -1)
+        rc = lib.lvq_voxel_slab_plan(ctypes.c_int64(ks), ctypes.c_int64(n), ctypes.c_int(hard), ctypes.byref(a) if ls else None,
+                                     ctypes.byref(b) if ns else None, c if caps else None)
+        return rc, a.value, b.value, list(c)
+
+    caps = [4096, 4096, 8192, 256]                      # DYN_VCAP, HARD_VCAP, HARD_PCAP, SMALL_PCAP
+    for ks, n, hard, want in [(512 * 512, 5420, 0, (15, 8)), (1024 * 1024 * 40, 5420, 0, (17, 320)), (2048 * 2048, 65536, 0, (15, 128)),
+                              (512 * 512, 5420, 1, (15, 8)), (1024 * 1024 * 40, 32768, 1, (17, 320)), (512 * 512, 32768, 0, (12, 64)),
+                              (1, 0, 0, (10, 1)), (1 << 30, 1, 1, (17, 8192)), ((1 << 31) - 1, 10 ** 6, 0, (18, 8192)),
+                              (25 * 1440 * 1440 * 40, 300000, 0, (18, 7911))]:
+        assert plan(ks, n, hard) == (0, *want, caps), (ks, n, hard)
+    # the hard kernels stop at slabs of 2^17 keys: the caller's next path takes a larger key space
+    assert plan((1 << 30) + 1, 5000, 1) == (-5, -1, -1, [-1] * 4)
+    assert plan((1 << 30) + 1, 5000, 0) == (0, 18, 4097, caps)
+    # refused before anything is written: null outputs, bad arguments, a key space of 2^31
+    for kw in (dict(ls=False), dict(ns=False), dict(caps=False)):
+        rc, a, b, c = plan(512 * 512, 5420, 0, **kw)
+        assert rc == -1 and (a, b, c) == (-1, -1, [-1] * 4)
+    assert plan(0, 5, 0)[0] == -1 and plan(-3, 5, 0)[0] == -1 and plan(100, -1, 0)[0] == -1 and plan(100, 5, 2)[0] == -1
+    for hard in (0, 1):
+        assert plan(1 << 31, 5420, hard) == (-4, -1, -1, [-1] * 4)
+        assert plan(26 * 1440 * 1440 * 40, 5420, hard)[0] == -4
+
+
 @pytest.fixture
 def fresh(lib, monkeypatch):
     """A handle loaded anew by _ffi.lib(): nothing but the loader has touched its function objects."""

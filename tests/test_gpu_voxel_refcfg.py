@@ -11,6 +11,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
+import voxel_slab_cases  # noqa: E402
 from lidar_vision_vqa_amd import _ffi as F  # noqa: E402
 from lidar_vision_vqa_amd import synth  # noqa: E402
 from oracle import lidar_oracle as LO  # noqa: E402
@@ -170,6 +171,8 @@ GUARD_CASES = {
     "hot_cells": lambda: [_hot_scene(77), np.zeros((0, 4), np.float32), _hot_scene(78)],
     "one_cell": lambda: [_one_cell_scene()],
     "tiny": lambda: [synth.scene_points("U", 1, 5), synth.scene_points("U", 63, 6)],
+    # one slab with 5120 voxels on either grid (tests/voxel_slab_cases.py): the slab kernels' counters and per-voxel state leave LDS
+    "dense_slab": voxel_slab_cases.guard_scenes,
 }
 
 
