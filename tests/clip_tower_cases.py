@@ -11,6 +11,9 @@ inputs, and a restatement of VitModel (deepencoder/clip_sdpa.py:123-365) written
                 "erf_gelu" (exact GELU in place of QuickGELU), "pos_truncated" (truncate / pad where the reference resamples), "no_pre_ln"
   embed / block / attention / feed_forward    single steps of the chain, for the module tests
   runtime_*     the DeepEncoder join: a small SAM, a CLIP of width 1024 and two layers, the 2048 x 2048 projector
+  DEEP / hidden_states / deep_hidden    the tower at 24 layers: its case, and the fp64 residual stream entering every block
+  view_image / view_pixels / join / runtime_full_ref    the join at the size DeepEncoderRuntime() builds (SAM ViT-B, the 24-layer CLIP),
+                restated in fp64 over vision_tower_cases.encoder and vit
 """
 import functools
 import math
@@ -37,16 +40,28 @@ CASES = {
     "own_patch": (BASE, (2, 3, 56, 56), None, 51, 157),
     "l2_w1024": (WIDE, (1, 3, 224, 224), (1, 1024, 16, 16), 52, 158),
 }
+# the tower at the depth it ships at (build_clip_l: 24 layers of width 1024).  A table of its own: CASES parametrises tests whose model
+# helper knows two geometries only.  Its state also serves the full-size runtime (RUNTIME_FULL) and every depth k <= 24: the keys of
+# layer i do not depend on num_layers
+DEEP = {
+    "l24_w1024": (dict(WIDE, num_layers=24), (1, 3, 224, 224), (1, 1024, 16, 16), 53, 159),
+}
+DEPTHS = (1, 2, 6, 12, 24)
 CLS_STD, POS_STD = 1.0, 0.5
 # with unit-gain MLP weights and biases ~ 0.02 N(0, 1) the `erf_gelu` variant moves the output by < 1e-2 (QuickGELU and exact GELU
 # differ by at most 0.02 anywhere); these two scales bring it to 0.13 while every other variant stays above 0.2
 FC1_BIAS_MEAN, FC2_GAIN = -2.0, 16.0
 VARIANTS = ("no_pos", "no_cls", "erf_gelu", "pos_truncated", "no_pre_ln")
-ROW_STEP = {"l2_w1024": 2}                               # rows kept in the golden: every second one (cls row 0 and the last row 256 among them)
+ROW_STEP = {"l2_w1024": 2, "l24_w1024": 2}              # rows kept in the golden: every second one (cls row 0 and the last row 256 among them)
 
 
 def golden_name(name):
     return f"clip_tower_{name}.npz"
+
+
+def case(name):
+    """(config, x shape, patch_embeds shape | None, weight seed, input seed) of a CASES or a DEEP entry."""
+    return CASES[name] if name in CASES else DEEP[name]
 
 
 def kept_rows(name, s):
@@ -57,7 +72,7 @@ def kept_rows(name, s):
 
 def case_inputs(name):
     """(x [B, 3, H, W], patch_embeds [B, C, Hs, Ws] | None), fp32."""
-    _, xs, ps, _, seed = CASES[name]
+    _, xs, ps, _, seed = case(name)
     return synth.randn(xs, seed), (None if ps is None else synth.randn(ps, seed + 1000))
 
 
@@ -94,7 +109,7 @@ def state(cfg, seed):
 
 @functools.lru_cache(maxsize=None)
 def case_state(name):
-    return state(CASES[name][0], CASES[name][3])
+    return state(case(name)[0], case(name)[3])
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
@@ -182,7 +197,24 @@ def vit(sd, cfg, x, patch_embeds, variant=None):
 def case_ref(name, variant=None):
     x, pe = case_inputs(name)
     with torch.no_grad():
-        return vit(case_state(name), CASES[name][0], x, pe, variant).numpy()
+        return vit(case_state(name), case(name)[0], x, pe, variant).numpy()
+
+
+def hidden_states(sd, cfg, x, patch_embeds):
+    """[h_0, ..., h_L] fp64: h_0 = embed(...), h_{i + 1} = block i of h_i.  h_k is vit() of the same state at num_layers = k (the keys of
+    a layer do not depend on the depth and vit ends on the last block), so one pass gives the reference of every depth and the input
+    of every block."""
+    with torch.no_grad():
+        hs = [embed(sd, cfg, x, patch_embeds)]
+        for i in range(cfg["num_layers"]):
+            hs.append(block(sd, f"transformer.layers.{i}.", cfg, hs[-1]))
+    return hs
+
+
+@functools.lru_cache(maxsize=None)
+def deep_hidden(name="l24_w1024"):
+    """hidden_states of a DEEP case (computed once, shared; callers must not write to it)."""
+    return tuple(hidden_states(case_state(name), case(name)[0], *case_inputs(name)))
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
@@ -210,3 +242,44 @@ def runtime_pixels():
 def projector_state():
     return {"layers.weight": synth.seeded_array("layers.weight", (2048, 2048), RUNTIME_SEEDS["projector"]),
             "layers.bias": synth.seeded_array("layers.bias", (2048,), RUNTIME_SEEDS["projector"])}
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# the join at the size DeepEncoderRuntime() builds: SAM ViT-B (vision_tower_cases: VIT_B, the state of its `vit_b_1024` case), the
+# 24-layer CLIP of DEEP, the same projector
+# --------------------------------------------------------------------------------------------------------------------------------
+RUNTIME_FULL_SAM, RUNTIME_FULL_CLIP = "vit_b_1024", "l24_w1024"
+RUNTIME_FULL_GOLDEN = "deepencoder_runtime_full.npz"
+N_VIEWS = 6
+
+
+def view_image(v):
+    """View v: the runtime image with its 64 x 64 blocks rolled by v (another picture per view, same statistics); view 0 is the image."""
+    return np.roll(runtime_image(), 64 * v, axis=(0, 1))
+
+
+def view_pixels(views):
+    """[len(views), 3, 1024, 1024] fp32 in [-1, 1]: _pil_to_tensor_og_norm of each view_image."""
+    arr = np.stack([view_image(v) for v in views]).astype(np.float32) / 255.0
+    return ((torch.from_numpy(arr).permute(0, 3, 1, 2) - 0.5) / 0.5).contiguous()
+
+
+def join(clip_out, sam_feats, proj):
+    """cat(clip[:, 1:], sam^T) @ W^T + b in fp64: clip_out [B, 1 + hw, Cc], sam_feats [B, Cs, g, g] -> [B, hw, n_embed]."""
+    fused = torch.cat((_d(clip_out)[:, 1:], _d(sam_feats).flatten(2).transpose(1, 2)), -1)
+    return fused @ _d(proj["layers.weight"]).t() + _d(proj["layers.bias"])
+
+
+@functools.lru_cache(maxsize=None)
+def runtime_full_ref(views=(0,)):
+    """The fp64 restatement of encode_pixels on view_pixels(views) at full size: VC.encoder -> vit conditioned on it -> join.
+    -> dict(sam [B, 1024, 16, 16], clip [B, 257, 1024], tokens [B, 256, 2048]) fp64 numpy (computed once, shared, read-only)."""
+    import vision_tower_cases as VC
+    x = view_pixels(views).numpy()
+    with torch.no_grad():
+        sam = VC.encoder(VC.VIT_B, VC.case_state(RUNTIME_FULL_SAM), x)
+        clip = vit(case_state(RUNTIME_FULL_CLIP), DEEP[RUNTIME_FULL_CLIP][0], x, sam)
+        out = dict(sam=sam, clip=clip.numpy(), tokens=join(clip, sam, projector_state()).numpy())
+    for a in out.values():
+        a.setflags(write=False)
+    return out

@@ -42,9 +42,7 @@ def runtime():
     return DE.DeepEncoderRuntime.from_modules(sam, clip, proj, device=DEV)
 
 
-def view_image(v):
-    """View v: the runtime image with its 64 x 64 blocks rolled by v (another picture per view, same statistics)."""
-    return np.roll(CC.runtime_image(), 64 * v, axis=(0, 1))
+view_image = CC.view_image                               # view v: the runtime image with its 64 x 64 blocks rolled by v
 
 
 def test_encode_pixels_reproduces_the_reference_runtime():

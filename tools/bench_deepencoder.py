@@ -15,7 +15,7 @@ forms.  Report only: this path has not been measured before, there is no referen
                 lvq_layernorm, and a second permute + lvq_cast_bf16 for the operand -- in alternation
   fc1_ab        fc1 with LVQ_GEMM_QUICK_GELU against fc1 to fp32 + a torch elementwise x sigmoid(1.702 x) + lvq_cast_bf16, in alternation
   depth24_error the 24-layer tower against an fp64 torch replay (tests/clip_tower_cases.py: vit) on the same seeded weights, both modes:
-                max |out - ref| / max(1, max|ref|).  No test covers depth 24; this figure is the only check of it.
+                max |out - ref| / max(1, max|ref|) (a report; tests/test_gpu_deepencoder_full.py holds depth 24 to its bounds)
 
     python tools/bench_deepencoder.py [--iters 10] [--reps 5] [--out profiles/deepencoder.json]
 """
@@ -153,7 +153,7 @@ def depth24_error(clip, sd, dev):
             got = clip(torch.from_numpy(x).to(dev), torch.from_numpy(pe).to(dev)).cpu().numpy()
         out[mode] = float(np.abs(got - ref).max()) / max(1.0, float(np.abs(ref).max()))
     out["max_abs_ref"] = float(np.abs(ref).max())
-    out["note"] = "24 layers, seeded weights (tests/clip_tower_cases.py scales), one image; measured once here -- no test covers depth 24"
+    out["note"] = "24 layers, seeded weights (tests/clip_tower_cases.py scales), one image"
     return out
 
 

@@ -7,17 +7,19 @@ stub of this tool's own: `easydict` (an attribute dict), `nuscenes.nuscenes` (an
 package (a bare namespace over the reference's directory, so its __init__ does not run).  Nothing that reaches the network is ever
 called: not DeepEncoderRuntime.__init__, not download_sam_if_needed, not load_openclip_vitl14_into_vitmodel, not deepencoder_infer.
 
-  clip_tower_<case>   per case of tests/clip_tower_cases.py: VitModel built from the configuration, every parameter loaded strictly from
-                      clip_tower_cases.case_state, eval() under no_grad() in fp32 -> `out` (the rows clip_tower_cases.kept_rows
-                      names), `rows`, and the state_dict's key list and shapes
+  clip_tower_<case>   per case of tests/clip_tower_cases.py (CASES, and DEEP: the 24-layer tower build_clip_l() ships): VitModel built
+                      from the configuration, every parameter loaded strictly from clip_tower_cases.case_state, eval() under no_grad()
+                      in fp32 -> `out` (the rows clip_tower_cases.kept_rows names), `rows`, and the state_dict's key list and shapes
   deepencoder_runtime a DeepEncoderRuntime made with object.__new__ whose sam / clip_vit / projector / device / dtype / grid / image_size
                       are set here (small SAM, CLIP of width 1024 and two layers, 2048 x 2048 projector, all seeded), and the unmodified
                       encode_image on a temporary PNG of clip_tower_cases.runtime_image() -> every fourth token row
+  deepencoder_runtime_full   the same at the size DeepEncoderRuntime() builds: the reference's ImageEncoderViT at the ViT-B geometry
+                      with the state of vision_tower_cases' `vit_b_1024` case, the 24-layer VitModel of DEEP, the same projector
   deepencoder_prep    resize_and_pad_to_square(im, target=64) and _pil_to_tensor_og_norm on a seeded 96 x 40 image
 
 Every file is data only and stays under 1 MiB (asserted).  No weights and no reference code are stored.
 
-    python tools/make_clip_tower_golden.py [case ... | runtime | prep]
+    python tools/make_clip_tower_golden.py [case ... | runtime | runtime_full | prep]
 """
 from __future__ import annotations
 
@@ -83,7 +85,7 @@ def load_strict(m, seeded):
 
 @torch.no_grad()
 def tower_case(clip, name):
-    cfg = CC.CASES[name][0]
+    cfg = CC.case(name)[0]
     m = load_strict(clip.VitModel(_AttrDict(cfg)), CC.case_state(name))
     x, pe = CC.case_inputs(name)
     out = m(torch.from_numpy(x), None if pe is None else torch.from_numpy(pe)).numpy()
@@ -94,14 +96,19 @@ def tower_case(clip, name):
 
 
 @torch.no_grad()
-def runtime_case(clip):
+def runtime_case(clip, full=False):
     from PIL import Image
     di = importlib.import_module("deepencoder.deepencoder_infer")
     sam_mod = importlib.import_module("deepencoder.sam_vary_sdpa")
     rt = object.__new__(di.DeepEncoderRuntime)
-    rt.sam = load_strict(sam_mod.ImageEncoderViT(**CC.RUNTIME_SAM, qkv_bias=True, use_rel_pos=True, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6)),
-                         VC.state(CC.RUNTIME_SAM, CC.RUNTIME_SEEDS["sam"]))
-    rt.clip_vit = load_strict(clip.VitModel(_AttrDict(CC.WIDE)), CC.state(CC.WIDE, CC.RUNTIME_SEEDS["clip"]))
+    if full:                                             # what DeepEncoderRuntime() builds: SAM ViT-B and the 24-layer CLIP
+        rt.sam = load_strict(sam_mod.ImageEncoderViT(**VC.VIT_B, qkv_bias=True, use_rel_pos=True, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6)),
+                             VC.case_state(CC.RUNTIME_FULL_SAM))
+        rt.clip_vit = load_strict(clip.VitModel(_AttrDict(CC.DEEP[CC.RUNTIME_FULL_CLIP][0])), CC.case_state(CC.RUNTIME_FULL_CLIP))
+    else:
+        rt.sam = load_strict(sam_mod.ImageEncoderViT(**CC.RUNTIME_SAM, qkv_bias=True, use_rel_pos=True, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6)),
+                             VC.state(CC.RUNTIME_SAM, CC.RUNTIME_SEEDS["sam"]))
+        rt.clip_vit = load_strict(clip.VitModel(_AttrDict(CC.WIDE)), CC.state(CC.WIDE, CC.RUNTIME_SEEDS["clip"]))
     rt.projector = load_strict(di.MlpProjector(di.EasyDict(projector_type="linear", input_dim=2048, n_embed=2048)), CC.projector_state())
     rt.device, rt.dtype, rt.grid, rt.image_size = "cpu", torch.float32, (di.FIXED_GRID_SIDE, di.FIXED_GRID_SIDE), di.FIXED_IMAGE_SIZE
     with tempfile.TemporaryDirectory() as tmp:
@@ -113,9 +120,9 @@ def runtime_case(clip):
     tok = res["tokens"].numpy()
     assert tok.shape == (256, 2048) and tuple(res["grid"]) == (16, 16) and res["image_size"] == 1024
     rows = np.arange(0, 256, CC.RUNTIME_ROW_STEP)
-    size = save(os.path.join(MG.OUT, "deepencoder_runtime.npz"), out=tok[rows], rows=rows, full_shape=np.array(tok.shape),
+    size = save(os.path.join(MG.OUT, CC.RUNTIME_FULL_GOLDEN if full else "deepencoder_runtime.npz"), out=tok[rows], rows=rows, full_shape=np.array(tok.shape),
                 result_keys=np.array(sorted(res)))
-    print(f"  runtime    {list(tok.shape)}  max {np.abs(tok).max():.3f}  {size / 1024:.0f} KiB")
+    print(f"  {'runtime_full' if full else 'runtime':12s} {list(tok.shape)}  max {np.abs(tok).max():.3f}  {size / 1024:.0f} KiB")
 
 
 def prep_case():
@@ -132,8 +139,8 @@ def main(names):
     install_stubs()
     clip = importlib.import_module("deepencoder.clip_sdpa")
     for name in names:
-        if name == "runtime":
-            runtime_case(clip)
+        if name in ("runtime", "runtime_full"):
+            runtime_case(clip, full=name == "runtime_full")
         elif name == "prep":
             prep_case()
         else:
@@ -141,4 +148,4 @@ def main(names):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or list(CC.CASES) + ["runtime", "prep"])
+    main(sys.argv[1:] or list(CC.CASES) + list(CC.DEEP) + ["runtime", "runtime_full", "prep"])
