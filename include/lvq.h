@@ -368,6 +368,33 @@ int lvq_attention_bf16_tiled_signed(const lvq_bf16 *q, const lvq_bf16 *q_lo, con
                                     int64_t kv_hstride, int64_t o_bstride, int64_t ldo, int64_t o_hstride, float scale, int k_fp16, lvq_bf16 *o,
                                     lvq_bf16 *o_lo, int32_t *stats, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
+/* Shared subtraction: the signed stream for a batch whose scenes have dirty cells in common (one sensor rig: ego surroundings, near-field
+ * ground).  A cell dirty in m of the batch's S scenes with 2 m > S + 1 is in the shared set G: its table row is subtracted ONCE per call (a
+ * B = 1 stream over the G list gives BASE = TOTALS - sum over G) and added back, as a plain key, in the S - m scenes where it is clean.
+ * Nothing is kept between calls; a batch without common cells gets an empty G and the lists and results of the two functions above.
+ * Cost rule, taken on the device from the counts: with a(s) / b(s) the tiles scene s streams with its plain pair list / with the shared lists
+ * (n_tiles when a list is not shorter than the full stream), G is used only when sum_s (a(s) - b(s)) exceeds the tiles of the G list;
+ * otherwise G counts as empty (a batch of mostly dirty scenes has a large G that hardly shortens any list).
+ *   lvq_bev_shared_lists: list_src [batch + 1, cap_tiles, 64] (cap_tiles >= n_tiles), list_info [batch + 1, 4]; entry `batch` is the G list.
+ *       A scene's list, in order: pair tiles (keys 0..31 = computed rows of its dirty cells outside G, keys 32..63 = the table rows of the
+ *       same cells, subtracted; last one padded with row 0 in both halves) | tiles of 64 plus keys, one per cell of G in key order (the
+ *       computed row where the scene is dirty, the table row where it is clean) | at most two remainder tiles of 32 plus keys whose keys
+ *       32..63 are ignored (row 0).  Every list has |G| plus keys, padded to a multiple of 32 with table row 0 -- the G list too, so the
+ *       padding is subtracted once and added back by every scene.  list_info[4 b] = tiles, [4 b + 1] = 1 when the list is shorter than the
+ *       full stream (else the batch runs row_src and ignores BASE), [4 b + 2] = first tile whose keys 32..63 are added (= pair tiles),
+ *       [4 b + 3] = first tile whose keys 32..63 are ignored.  Workspace: 64 n_tiles + 512 (batch + 1) + 512 bytes.
+ *   lvq_attention_bf16_tiled_shared: as lvq_attention_bf16_tiled_signed with those lists (one copy of q for all batches);
+ *       totals_k_fp16 = the k_fp16 the totals were taken with (the G stream uses the same operand form).  The cancellation check and
+ *       the guard statistics judge against TOTALS as before.  Workspace: lvq_attention_tiled_signed_workspace_bytes (covers both). */
+int lvq_bev_shared_lists(const int32_t *row_src, int batch, int n_tiles, int row_base, int cap_tiles, int32_t *list_src, int32_t *list_info,
+                         void *ws, size_t ws_bytes, lvq_stream_t stream);
+int lvq_attention_bf16_tiled_shared(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *k_rows, const lvq_bf16 *v_rows,
+                                    const int32_t *row_src, const int32_t *list_src, const int32_t *list_info, int list_cap_tiles,
+                                    const float *totals, int totals_k_fp16, int batch, int n_heads, int nq, int n_tiles, int dh,
+                                    int64_t ldq, int64_t q_hstride, int64_t ldkv, int64_t kv_hstride, int64_t o_bstride, int64_t ldo,
+                                    int64_t o_hstride, float scale, int k_fp16, lvq_bf16 *o, lvq_bf16 *o_lo, int32_t *stats, void *ws,
+                                    size_t ws_bytes, lvq_stream_t stream);
+
 /* Guard of the plain-bf16 key stream ("mixed" modes), per-model half: g[h * nq + i] = (1 + max_k |scale q_i . k_k|) / sqrt(N_eff)
  * with N_eff = (sum_k p_k)^2 / sum_k p_k^2, p = softmax weights of query i of head h over the nkv key rows (head_dim 64, nkv % 4 == 0; plain
  * bf16 operands -- a statistic, not a result).  The error that plain K / V / P leave in the attention output grows like max(g)

@@ -46,6 +46,11 @@ struct AttnArgs {
     const int32_t *pair_src, *pair_info;
     int pair_cap;
     const float *totals;
+    // shared subtraction (k_attn32<., ., 3>, lvq_attention_bf16_tiled_shared): the lists of lvq_bev_shared_lists -- pair_info has FOUR words
+    // per batch (tiles | use | first tile whose keys 32..63 are ADDED | first tile whose keys 32..63 are IGNORED); the combine adds `base`
+    // (totals minus the batch-wide G stream) instead of `totals`, and keeps judging against `totals`
+    const float *base;
+    int pair_iw;              // words of pair_info per batch as the combine kernel reads it (0 = 2)
     int32_t *flags;           // out, per (b, h): the signed result of some query is unusable (non-finite, or cancellation too deep)
     const int32_t *pred;      // in, per (b, h): workgroups / rows of (b, h) with pred == 0 do nothing (the predicated full re-run)
     int force_part;           // write partials even when nsplit == 1
@@ -643,10 +648,22 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
     bool fresh = true;
 
     // TL == 2: this batch's stream is its pair list (signed) or, when that would not be shorter, its full tile list (unsigned)
-    const int pair_mode = TL == 2 ? __builtin_amdgcn_readfirstlane(a.pair_info[2 * b + 1]) : 0;
+    // TL == 3: the same with the lists of the shared subtraction -- what happens to keys 32..63 depends on the TILE: subtracted below tile
+    // t_add, added below tile t_ign, ignored from there on (wave-uniform scalars; P >= 0, so its sign bits are set with an OR)
+    constexpr int PIW = TL == 3 ? 4 : 2;                        // words of pair_info per batch
+    const int pair_mode = TL >= 2 ? __builtin_amdgcn_readfirstlane(a.pair_info[PIW * b + 1]) : 0;
     const uint32_t smask = pair_mode ? 0x80008000u : 0u;        // sign bits of a packed bf16 pair
     const uint32_t lsign = pair_mode ? 0x80000000u : 0u;
-    const int n_tiles = pair_mode ? __builtin_amdgcn_readfirstlane(a.pair_info[2 * b]) : a.Nkv / KVB;
+    const int n_tiles = pair_mode ? __builtin_amdgcn_readfirstlane(a.pair_info[PIW * b]) : a.Nkv / KVB;
+    const int t_add = (TL == 3 && pair_mode) ? __builtin_amdgcn_readfirstlane(a.pair_info[4 * b + 2]) : 0;
+    const int t_ign = (TL == 3 && pair_mode) ? __builtin_amdgcn_readfirstlane(a.pair_info[4 * b + 3]) : 0x7fffffff;
+    [[maybe_unused]] uint32_t p_and = 0xffffffffu, p_or = 0u;   // TL == 3: P of keys 32..63 of the current tile = (P & p_and) | p_or
+    [[maybe_unused]] float l_mul = 1.0f;                        //          and their row sum times l_mul
+    [[maybe_unused]] auto tile_op = [&](int t) __attribute__((always_inline)) {
+        p_and = t < t_ign ? 0xffffffffu : 0u;
+        p_or = t < t_add ? 0x80008000u : 0u;
+        l_mul = t < t_add ? -1.0f : t < t_ign ? 1.0f : 0.0f;
+    };
     const int tps = (n_tiles + a.nsplit - 1) / a.nsplit;
     const int t0 = sp * tps;
     const int t1 = t0 + tps < n_tiles ? t0 + tps : n_tiles;
@@ -822,7 +839,8 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
 #pragma unroll
         for (int d = 0; d < 2; ++d)
             vlane[par][d] = (uint32_t)(2 * (rb * KROW + (((d * 4 + ch0) ^ (f_even ^ (par << 1))) << 3) + 4 * (pp & 1)));
-    auto tile_fast = [&](const uint16_t *Ks, const uint16_t *Vs) __attribute__((always_inline)) {
+    auto tile_fast = [&](const uint16_t *Ks, const uint16_t *Vs, [[maybe_unused]] int t) __attribute__((always_inline)) {
+        if (TL == 3) tile_op(t);
         const uint32_t vb = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint16_t *)Vs);
         const uint32_t e0 = vb + vlane[0][0], e1 = vb + vlane[0][1], o0 = vb + vlane[1][0], o1 = vb + vlane[1][1];
 #pragma unroll
@@ -855,8 +873,10 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
                 ls += x0 + x1;
                 pk[e] = pack_bf16(x0, x1);
                 if (TL == 2 && kb == 1) pk[e] ^= smask;        // -P for the subtracted half of a pair tile
+                if (TL == 3 && kb == 1) pk[e] = (pk[e] & p_and) | p_or;
             }
-            lsum += (TL == 2 && kb == 1) ? __uint_as_float(__float_as_uint(ls) ^ lsign) : ls;   // the subtracted half's row sum
+            if (TL == 3 && kb == 1) lsum = fmaf(ls, l_mul, lsum);
+            else lsum += (TL == 2 && kb == 1) ? __uint_as_float(__float_as_uint(ls) ^ lsign) : ls;   // the subtracted half's row sum
             uint4 u0 = make_uint4(pk[0], pk[1], pk[2], pk[3]), u1 = make_uint4(pk[4], pk[5], pk[6], pk[7]);
             const bf16x8 pf0 = *reinterpret_cast<bf16x8 *>(&u0), pf1 = *reinterpret_cast<bf16x8 *>(&u1);
             lds_tr_wait4(a00, a01, a10, a11);
@@ -917,14 +937,16 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
         auto soft_f = [&](int g, auto neg_tag) __attribute__((always_inline)) {
             const float x0 = xa[g & 1], x1 = xb[g & 1];
             tg[g] = x0 + x1;
-            pk[g] = decltype(neg_tag)::value ? pack_bf16(-x0, -x1) : pack_bf16(x0, x1);
+            constexpr int NEGK = decltype(neg_tag)::value;         // 0: added, 1: subtracted, 2: the tile's operation (TL == 3)
+            pk[g] = NEGK == 1 ? pack_bf16(-x0, -x1) : pack_bf16(x0, x1);
+            if (NEGK == 2) pk[g] = (pk[g] & p_and) | p_or;
             asm volatile("" : "+v"(tg[g]), "+v"(pk[g]));           // computed HERE: the IR sinks unpinned values past B1 to their first use
         };
         // O += V P of one block with the row-sum chain in the gaps (the last group's soft_f first)
         // (single-pass score forms, NM == 4: a block has 4 score MFMAs for the same 16 exponentials, so the last two groups of a block's
         // softmax run in the first two PV gaps -- the second half of P, pf1, is only needed by the third PV MFMA)
         auto pv = [&](auto neg_tag, auto &&after_second, const f32x16 &sc) __attribute__((always_inline)) {
-            constexpr bool NEG = decltype(neg_tag)::value;
+            constexpr int NEG = decltype(neg_tag)::value;
             if (NM == 8) soft_f(7, neg_tag);
             uint4 u0 = make_uint4(pk[0], pk[1], pk[2], pk[3]);
             const bf16x8 pf0 = *reinterpret_cast<bf16x8 *>(&u0);
@@ -946,7 +968,7 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
             __builtin_amdgcn_sched_barrier(0);
             o[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_shufflevector(va[6], va[7], 0, 1, 2, 3, 4, 5, 6, 7), pf1, o[1], 0, 0, 0);
             ls += tg[6]; ls += tg[7];
-            lsum = NEG ? lsum - ls : lsum + ls;
+            lsum = NEG == 2 ? fmaf(ls, l_mul, lsum) : NEG ? lsum - ls : lsum + ls;
             __builtin_amdgcn_sched_barrier(0);
         };
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -988,6 +1010,7 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
         auto body = [&](int t, auto more_tag, auto neg_tag) __attribute__((always_inline)) {
             constexpr bool MORE = decltype(more_tag)::value;       // a tile t+1 exists
             const int sl = (t - t0) & 3;
+            if (decltype(neg_tag)::value == 2) tile_op(t);
             const uint32_t sb = sbase + (uint32_t)sl * (uint32_t)(TILE_E * 2);
             const uint32_t sb1 = sbase + (uint32_t)((sl + 1) & 3) * (uint32_t)(TILE_E * 2);
             // P1
@@ -1040,7 +1063,10 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
             pv(neg_tag, []() __attribute__((always_inline)) {}, sc1);
         };
         int t = t0;
-        if (TL == 2 && pair_mode) {                                // keys 32..63 of every tile are subtracted
+        if (TL == 3 && pair_mode) {                                // keys 32..63: subtracted, added or ignored, by tile
+            for (; t + 1 < t1; ++t) body(t, std::true_type{}, std::integral_constant<int, 2>{});
+            body(t, std::false_type{}, std::integral_constant<int, 2>{});
+        } else if (TL == 2 && pair_mode) {                         // keys 32..63 of every tile are subtracted
             for (; t + 1 < t1; ++t) body(t, std::true_type{}, std::true_type{});
             body(t, std::false_type{}, std::true_type{});
         } else {
@@ -1112,7 +1138,7 @@ __global__ void __launch_bounds__(NW * 64, PIPE ? 2 : 3) k_attn32(AttnArgs a) {
         for (; t < t1; ++t) {
             pre(t);
             if (!SLOW) {
-                tile_fast(smem + slot * TILE_E, smem + slot * TILE_E + KVB * KROW);
+                tile_fast(smem + slot * TILE_E, smem + slot * TILE_E + KVB * KROW, t);
                 post(t);
                 continue;
             }
@@ -1274,18 +1300,20 @@ __global__ void __launch_bounds__(256) k_attn_combine_signed(AttnArgs a) {
     const bool live = idx < total && !(a.pred && a.pred[bh] == 0);
     if (!live && !slots) return;                                // (the predicated re-run's merge: rows of unflagged (b, h) leave at once)
     const int stride = a.dh + 2;
-    const bool signed_b = !a.pred && a.pair_info && a.pair_info[2 * b + 1] != 0;
+    const bool signed_b = !a.pred && a.pair_info && a.pair_info[(a.pair_iw ? a.pair_iw : 2) * b + 1] != 0;
     const float *tot = signed_b ? a.totals + ((int64_t)h * a.Nq + qi) * stride : nullptr;
-    float M = tot ? tot[a.dh] : -INFINITY;
+    // shared subtraction: the sums start from BASE = TOTALS - (the batch's G stream); lt, what the result is judged against, stays the table's
+    const float *bas = (signed_b && a.base) ? a.base + ((int64_t)h * a.Nq + qi) * stride : tot;
+    float M = tot ? fmaxf(tot[a.dh], bas[a.dh]) : -INFINITY;
     for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, a.part[((bh * a.nsplit + s) * a.Nq + qi) * stride + a.dh]);
     const float Ms = (M == -INFINITY) ? 0.f : M;
     float acc[4] = {0.f, 0.f, 0.f, 0.f}, l = 0.f, lt = 0.f;
     if (tot) {
-        const float w = exp2f(tot[a.dh] - Ms);
-        lt = w * tot[a.dh + 1];
-        l = lt;
+        const float w = exp2f(bas[a.dh] - Ms);
+        lt = exp2f(tot[a.dh] - Ms) * tot[a.dh + 1];
+        l = w * bas[a.dh + 1];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) acc[r] = w * tot[d0 + r];
+        for (int r = 0; r < 4; ++r) acc[r] = w * bas[d0 + r];
     }
     for (int s = 0; s < a.nsplit; ++s) {
         const float *pr = a.part + ((bh * a.nsplit + s) * a.Nq + qi) * stride;
@@ -1364,6 +1392,38 @@ __global__ void __launch_bounds__(256) k_attn_combine_raw(AttnArgs a, float *__r
         for (int r = 0; r < 4; ++r) acc[r] += w * pr[d0 + r];
     }
     float *dst = totals + (bh * a.Nq + qi) * stride;
+    *reinterpret_cast<f32x4 *>(dst + d0) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    if (d0 == 0) { dst[a.dh] = Ms; dst[a.dh + 1] = l; }
+}
+
+// shared subtraction: merge the KV splits of the B = 1 stream over the G list and take them off the table totals,
+// base[h][qi] = totals[h][qi] - sum_s w_s (O_s | l_s), in the common reference max(m_totals, max_s m_s).  An empty G list leaves base == totals bit for bit.
+__global__ void __launch_bounds__(256) k_attn_combine_base(AttnArgs a, const float *__restrict__ totals, float *__restrict__ base) {
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int dq = a.dh / 4;
+    const int64_t total = (int64_t)a.H * a.Nq * dq;
+    if (idx >= total) return;
+    const int d0 = (int)(idx % dq) * 4;
+    const int64_t row = idx / dq;                    // h * Nq + qi
+    const int qi = (int)(row % a.Nq);
+    const int64_t bh = row / a.Nq;
+    const int stride = a.dh + 2;
+    const float *tot = totals + row * stride;
+    float M = tot[a.dh];
+    for (int s = 0; s < a.nsplit; ++s) M = fmaxf(M, a.part[((bh * a.nsplit + s) * a.Nq + qi) * stride + a.dh]);
+    const float Ms = (M == -INFINITY) ? 0.f : M;
+    const float wt = exp2f(tot[a.dh] - Ms);
+    float acc[4], l = wt * tot[a.dh + 1];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = wt * tot[d0 + r];
+    for (int s = 0; s < a.nsplit; ++s) {
+        const float *pr = a.part + ((bh * a.nsplit + s) * a.Nq + qi) * stride;
+        const float w = exp2f(pr[a.dh] - Ms);
+        l -= w * pr[a.dh + 1];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] -= w * pr[d0 + r];
+    }
+    float *dst = base + row * stride;
     *reinterpret_cast<f32x4 *>(dst + d0) = f32x4{acc[0], acc[1], acc[2], acc[3]};
     if (d0 == 0) { dst[a.dh] = Ms; dst[a.dh + 1] = l; }
 }
@@ -1760,8 +1820,11 @@ extern "C" size_t lvq_attention_tiled_signed_workspace_bytes(int batch, int n_he
     if (nkv > 0x7fffffff) return 0;
     const AttnPlan pl = plan_k32_any(batch, n_heads, nq, (int)nkv, dh);
     if (!pl.k32) return 0;
+    // (+ what lvq_attention_bf16_tiled_shared adds: the partials of its B = 1 stream over the G list and BASE)
+    const AttnPlan p1 = plan_k32_any(1, n_heads, nq, (int)nkv, dh);
     return (size_t)batch * n_heads * pl.nsplit * nq * (dh + 2) * sizeof(float) + (size_t)batch * n_heads * sizeof(int32_t) +
-           (size_t)STAT_SLOTS * 64 * sizeof(int32_t) + 768;
+           (size_t)STAT_SLOTS * 64 * sizeof(int32_t) + 768 +
+           lvq_align((size_t)n_heads * p1.nsplit * nq * (dh + 2) * sizeof(float)) + lvq_align((size_t)n_heads * nq * (dh + 2) * sizeof(float)) + 512;
 }
 
 // As lvq_attention_bf16_tiled, with the per-batch pair lists of lvq_bev_scene_pairs and the per-model totals.  The queries must be the
@@ -1817,6 +1880,90 @@ extern "C" int lvq_attention_bf16_tiled_signed(const lvq_bf16 *q, const lvq_bf16
     hipLaunchKernelGGL(k_attn_combine_signed, dim3((unsigned)lvq_cdiv(total, 256)), dim3(256), 0, st, a);
     // predicated full re-run of the flagged (batch, head) pairs: every workgroup of an unflagged pair returns at once
     a.flags = nullptr; a.pred = flags; a.pair_src = nullptr; a.pair_info = nullptr; a.totals = nullptr;      // (stats / stat_slots stay: folded by this merge)
+    launch_k32<1>(a, pl.k32, qs, nwg, lds, st);
+    hipLaunchKernelGGL(k_attn_combine_signed, dim3((unsigned)lvq_cdiv(total, 256)), dim3(256), 0, st, a);
+    return lvq_launch_status();
+}
+
+// ---- shared subtraction: the signed stream with the table rows that most scenes of the batch subtract taken off ONCE ----------------
+// For a cell that is dirty in m of the batch's S scenes, the signed stream above recomputes the same table term w(c) in m scenes.  With
+// G = {c : 2 m > S + 1} (lvq_bev_shared_lists), BASE = TOTALS - sum over G of w(c) is formed once per call by a B = 1 stream over the G
+// list, and a scene streams: pairs for its dirty cells outside G, its computed rows for its dirty cells in G, and the table rows of the
+// cells of G where it is clean (added back).  Same operand bits on both sides of every cancellation as in the signed stream; the G stream
+// runs in the operand form the totals were taken in (totals_k_fp16).  Scenes that run their full list ignore BASE as they ignore TOTALS.
+// Workspace: lvq_attention_tiled_signed_workspace_bytes (it covers both functions).
+extern "C" int lvq_attention_bf16_tiled_shared(const lvq_bf16 *q, const lvq_bf16 *q_lo, const lvq_bf16 *k_rows, const lvq_bf16 *v_rows,
+                                               const int32_t *row_src, const int32_t *list_src, const int32_t *list_info, int list_cap_tiles,
+                                               const float *totals, int totals_k_fp16, int batch, int n_heads, int nq, int n_tiles, int dh,
+                                               int64_t ldq, int64_t q_hstride, int64_t ldkv, int64_t kv_hstride, int64_t o_bstride, int64_t ldo,
+                                               int64_t o_hstride, float scale, int k_fp16, lvq_bf16 *o, lvq_bf16 *o_lo, int32_t *stats, void *ws,
+                                               size_t ws_bytes, lvq_stream_t stream) {
+    if (batch <= 0 || n_heads <= 0 || nq < 0 || n_tiles <= 0 || list_cap_tiles <= 0 || !q || !k_rows || !v_rows || !row_src || !list_src ||
+        !list_info || !totals || !o)
+        return LVQ_EINVAL;
+    if (nq == 0) return LVQ_OK;
+    const int64_t nkv64 = (int64_t)n_tiles * KVB;
+    if (nkv64 > 0x7fffffff) return LVQ_EUNSUPPORTED;
+    const int nkv = (int)nkv64;
+    if (dh != 64 || (ldq & 7) || (ldkv & 7) || ldkv <= 0 || ldkv > 0x7fffffff || (q_hstride & 7) || (kv_hstride & 7) || (ldo & 3) ||
+        (o_hstride & 3) || (o_bstride & 3))
+        return LVQ_EUNSUPPORTED;
+    if (((uintptr_t)q | (uintptr_t)q_lo | (uintptr_t)k_rows | (uintptr_t)v_rows | (uintptr_t)row_src | (uintptr_t)list_src | (uintptr_t)totals) & 15)
+        return LVQ_EUNSUPPORTED;
+    if (((uintptr_t)o | (uintptr_t)o_lo) & 7) return LVQ_EUNSUPPORTED;
+    if (n_heads > 65535 || batch > 65534 || list_cap_tiles < n_tiles) return LVQ_EUNSUPPORTED;
+    if (totals_k_fp16 && !k_fp16) return LVQ_EINVAL;
+    const int qs = k_fp16 ? 2 : (q_lo != nullptr ? 1 : 0);
+    const int qs1 = totals_k_fp16 == 2 ? 3 : qs;                 // the G stream: the operand form of the totals
+    const AttnPlan pl = plan_attn(batch, n_heads, nq, nkv, dh, false, true, qs);
+    const AttnPlan p1 = plan_attn(1, n_heads, nq, nkv, dh, false, true, qs1 == 3 ? 0 : qs1);
+    if (!pl.k32 || !p1.k32) return LVQ_EUNSUPPORTED;
+    AttnArgs a{};
+    a.q = q; a.ql = q_lo; a.k = k_rows; a.v = v_rows;
+    a.B = batch; a.H = n_heads; a.Hkv = n_heads; a.Nq = nq; a.Nkv = nkv; a.dh = dh;
+    a.q_bs = 0; a.ldq = ldq; a.q_hs = q_hstride; a.ldk = ldkv; a.k_hs = kv_hstride; a.ldv = ldkv; a.v_hs = kv_hstride;
+    a.o_bs = o_bstride; a.ldo = ldo; a.o_hs = o_hstride; a.scale = scale; a.o = o; a.ol = o_lo;
+    a.row_src = row_src;
+    a.pair_src = list_src; a.pair_info = list_info; a.pair_cap = list_cap_tiles; a.totals = totals; a.pair_iw = 4;
+    a.nsplit = pl.nsplit; a.nqt = pl.nqt; a.force_part = 1;
+    LvqArena arena(ws, ws_bytes);
+    a.part = arena.take<float>((size_t)batch * n_heads * pl.nsplit * nq * (dh + 2));
+    int32_t *flags = arena.take<int32_t>((size_t)batch * n_heads);
+    int32_t *stat_slots = stats ? arena.take<int32_t>((size_t)STAT_SLOTS * 64) : nullptr;
+    float *part1 = arena.take<float>((size_t)n_heads * p1.nsplit * nq * (dh + 2));
+    float *base = arena.take<float>((size_t)n_heads * nq * (dh + 2));
+    if (!arena.ok) return LVQ_EWORKSPACE;
+    hipStream_t st = lvq_s(stream);
+    const size_t lds = K32_LDS_TILED;
+    const int64_t ngrp = (int64_t)a.B * a.H * a.nsplit;
+    const int64_t nwg = (ngrp + 7) / 8 * 8 * a.nqt;
+    if (nwg > 0x7fffffff) return LVQ_EUNSUPPORTED;
+    const int64_t total = (int64_t)a.B * a.H * a.Nq * (a.dh / 4);
+    if (hipMemsetAsync(flags, 0, (size_t)batch * n_heads * sizeof(int32_t), st) != hipSuccess) return LVQ_ELAUNCH;
+    if (stat_slots && hipMemsetAsync(stat_slots, 0, (size_t)STAT_SLOTS * 64 * sizeof(int32_t), st) != hipSuccess) return LVQ_ELAUNCH;
+    {   // the G stream (entry `batch` of the lists) with B = 1, and BASE
+        AttnArgs g = a;
+        g.B = 1; g.o = nullptr; g.ol = nullptr; g.totals = nullptr;
+        g.pair_src = list_src + (int64_t)batch * list_cap_tiles * KVB; g.pair_info = list_info + 4 * (int64_t)batch;
+        g.nsplit = p1.nsplit; g.nqt = p1.nqt; g.part = part1;
+        const int64_t nwg1 = ((int64_t)g.H * g.nsplit + 7) / 8 * 8 * g.nqt;
+        if (qs1 == 3) {
+            if (p1.k32 == 6) hipLaunchKernelGGL((k_attn32<6, 3, 3>), dim3((unsigned)nwg1), dim3(384), lds, st, g);
+            else             hipLaunchKernelGGL((k_attn32<4, 3, 3>), dim3((unsigned)nwg1), dim3(256), lds, st, g);
+        } else {
+            launch_k32<3>(g, p1.k32, qs1, nwg1, lds, st);
+        }
+        const int64_t total1 = (int64_t)g.H * g.Nq * (g.dh / 4);
+        hipLaunchKernelGGL(k_attn_combine_base, dim3((unsigned)lvq_cdiv(total1, 256)), dim3(256), 0, st, g, totals, base);
+    }
+    a.base = base;
+    a.flags = flags;
+    a.stats = stats;
+    a.stat_slots = stat_slots;
+    launch_k32<3>(a, pl.k32, qs, nwg, lds, st);
+    hipLaunchKernelGGL(k_attn_combine_signed, dim3((unsigned)lvq_cdiv(total, 256)), dim3(256), 0, st, a);
+    // predicated full re-run of the flagged (batch, head) pairs, as in the signed stream
+    a.flags = nullptr; a.pred = flags; a.pair_src = nullptr; a.pair_info = nullptr; a.totals = nullptr; a.base = nullptr;
     launch_k32<1>(a, pl.k32, qs, nwg, lds, st);
     hipLaunchKernelGGL(k_attn_combine_signed, dim3((unsigned)lvq_cdiv(total, 256)), dim3(256), 0, st, a);
     return lvq_launch_status();

@@ -318,6 +318,168 @@ __global__ void __launch_bounds__(PAIR2_NT) k_scene_pair_write(const int32_t *__
     }
 }
 
+// ---- shared subtraction (lvq_bev_shared_lists, DESIGN 3.2 "Shared subtraction"): a cell that is dirty in m of the S scenes of a batch
+// with 2 m > S + 1 goes into the shared set G.  Its table row is subtracted ONCE for the whole batch (the G list, streamed with B = 1) and
+// added back in the scenes where the cell is clean.  A scene's list: pair tiles (32 computed rows | the 32 table rows of the same cells) of its
+// dirty cells outside G, then ONE plus slot per cell of G in key order (the computed row where the scene is dirty, the table row where it is
+// clean) in tiles of 64, then at most two remainder tiles of 32 plus slots whose second half is ignored.  Every scene has exactly |G| plus
+// slots and the G list has |G| rows, so all of them pad to the same multiple of 32 with table row 0: the G list subtracts those copies
+// of row 0 and every scene that uses its list adds them back.
+constexpr int SH_NT = 256;
+// pass 1: flag[e] = 1 when cell e is in G
+__global__ void __launch_bounds__(SH_NT) k_shared_flags(const int32_t *__restrict__ row_src, int S, int ne, int row_base, uint8_t *__restrict__ flag) {
+    const int e = ((int)blockIdx.x * SH_NT + (int)threadIdx.x) * 4;
+    if (e >= ne) return;
+    int m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    for (int s = 0; s < S; ++s) {
+        const int4 v = *reinterpret_cast<const int4 *>(row_src + (int64_t)s * ne + e);
+        m0 += v.x >= row_base; m1 += v.y >= row_base; m2 += v.z >= row_base; m3 += v.w >= row_base;
+    }
+    const int thr = S + 1;
+    *reinterpret_cast<uint32_t *>(flag + e) = (uint32_t)(2 * m0 > thr) | ((uint32_t)(2 * m1 > thr) << 8) | ((uint32_t)(2 * m2 > thr) << 16) |
+                                              ((uint32_t)(2 * m3 > thr) << 24);
+}
+// pass 2: per scene and chunk the dirty cells outside G (cnt[s * 64 + ch]) and inside G (cnt[(S + 1 + s) * 64 + ch]); per chunk the cells of
+// G (cnt[S * 64 + ch], by the blocks of scene 0)
+__global__ void __launch_bounds__(SH_NT) k_shared_count(const int32_t *__restrict__ row_src, const uint8_t *__restrict__ flag, int S, int nt, int row_base,
+                                                        int chunk, int32_t *__restrict__ cnt) {
+    __shared__ int wsum[SH_NT / 64][3];
+    const int ch = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int ne = nt * TCELLS;
+    const int32_t *src = row_src + (int64_t)s * ne;
+    const int e_end = (ch + 1) * chunk < ne ? (ch + 1) * chunk : ne;
+    int c = 0, g = 0, dg = 0;
+    for (int e = ch * chunk + tid * 4; e < e_end; e += SH_NT * 4) {
+        const int4 v = *reinterpret_cast<const int4 *>(src + e);
+        const uint32_t f = *reinterpret_cast<const uint32_t *>(flag + e);
+        const int f0 = f & 1, f1 = (f >> 8) & 1, f2 = (f >> 16) & 1, f3 = (f >> 24) & 1;
+        c += (v.x >= row_base && !f0) + (v.y >= row_base && !f1) + (v.z >= row_base && !f2) + (v.w >= row_base && !f3);
+        dg += (v.x >= row_base && f0) + (v.y >= row_base && f1) + (v.z >= row_base && f2) + (v.w >= row_base && f3);
+        g += f0 + f1 + f2 + f3;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { c += __shfl_xor(c, o); g += __shfl_xor(g, o); dg += __shfl_xor(dg, o); }
+    if (lane == 0) { wsum[wid][0] = c; wsum[wid][1] = g; wsum[wid][2] = dg; }
+    __syncthreads();
+    if (tid == 0) {
+        cnt[s * 64 + ch] = wsum[0][0] + wsum[1][0] + wsum[2][0] + wsum[3][0];
+        cnt[(S + 1 + s) * 64 + ch] = wsum[0][2] + wsum[1][2] + wsum[2][2] + wsum[3][2];
+        if (s == 0) cnt[S * 64 + ch] = wsum[0][1] + wsum[1][1] + wsum[2][1] + wsum[3][1];
+    }
+}
+// pass 3: the lists.  First the batch's cost rule, from the counts alone (every workgroup takes the same decision): with a(s) / b(s) the tiles
+// scene s would stream with its plain pair list / with the shared lists (n_tiles when the list is not shorter than the full stream), G is
+// used only when sum_s (a(s) - b(s)) exceeds the tiles of the G list itself -- a batch of mostly dirty scenes has a large G that hardly
+// shortens any list.  Otherwise G counts as empty: plain pair lists, an empty G list.  blockIdx.y = S writes the G list (no pair tiles, the table row of every cell of G).  info[4 s] = tiles (0 when unused),
+// [4 s + 1] = use, [4 s + 2] = first tile whose second half is ADDED (= pair tiles), [4 s + 3] = first tile whose second half is IGNORED.
+__global__ void __launch_bounds__(SH_NT) k_shared_write(const int32_t *__restrict__ row_src, const uint8_t *__restrict__ flag, int S, int nt, int row_base,
+                                                        int cap, int chunk, int nch, const int32_t *__restrict__ cnt, int32_t *__restrict__ list_src,
+                                                        int32_t *__restrict__ info) {
+    __shared__ int wsum[SH_NT / 64];
+    __shared__ int l_start[6];
+    __shared__ int l_gain;
+    const int ch = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const bool isg = s == S;
+    const int ne = nt * TCELLS;
+    const int32_t *src = row_src + (int64_t)(isg ? 0 : s) * ne;
+    int32_t *dst = list_src + (int64_t)s * cap * TCELLS;
+    if (tid < 64) {
+        const int vp = (tid < nch && !isg) ? cnt[s * 64 + tid] : 0, vg = tid < nch ? cnt[S * 64 + tid] : 0;
+        const int vd = (tid < nch && !isg) ? cnt[(S + 1 + s) * 64 + tid] : 0;
+        int bp = tid < ch ? vp : 0, ap = vp, bg = tid < ch ? vg : 0, ag = vg, bd = tid < ch ? vd : 0, ad = vd;
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) {
+            bp += __shfl_xor(bp, o); ap += __shfl_xor(ap, o); bg += __shfl_xor(bg, o); ag += __shfl_xor(ag, o);
+            bd += __shfl_xor(bd, o); ad += __shfl_xor(ad, o);
+        }
+        if (tid == 0) { l_start[0] = bp; l_start[1] = ap; l_start[2] = bg; l_start[3] = ag; l_start[4] = bd; l_start[5] = ad; l_gain = 0; }
+    }
+    __syncthreads();
+    const int g_tiles = (l_start[3] >> 6) + (((l_start[3] + 31) >> 5) - 2 * (l_start[3] >> 6));      // tiles of the G list
+    for (int sc = tid; sc < S; sc += SH_NT) {
+        int np = 0, nd = 0;
+        for (int q = 0; q < nch; ++q) { np += cnt[sc * 64 + q]; nd += cnt[(S + 1 + sc) * 64 + q]; }
+        int a = (np + nd + 31) >> 5, b = ((np + 31) >> 5) + g_tiles;
+        a = a < nt ? a : nt;
+        b = b < nt ? b : nt;
+        if (a != b) atomicAdd(&l_gain, a - b);
+    }
+    __syncthreads();
+    const bool share = l_gain > g_tiles;
+    int run_p = l_start[0] + (share ? 0 : l_start[4]), run_g = share ? l_start[2] : 0;
+    const int n_pair = l_start[1] + (share ? 0 : l_start[5]), n_g = share ? l_start[3] : 0;
+    const int n_pt = (n_pair + 31) >> 5;                         // pair tiles
+    const int n_full = n_g >> 6, n_half = (n_g + 31) >> 5;       // tiles of 64 plus slots; 32-slot halves in all
+    const int n_all = n_pt + n_full + (n_half - 2 * n_full);
+    // plus slot j (its cell's rank in G) -> word of the list, or -1 past the capacity
+    auto plus_pos = [&](int j) {
+        const int r = j - 64 * n_full;
+        const int t = r < 0 ? n_pt + (j >> 6) : n_pt + n_full + (r >> 5);
+        return t < cap ? t * TCELLS + (r < 0 ? (j & 63) : (r & 31)) : -1;
+    };
+    const int e_end = (ch + 1) * chunk < ne ? (ch + 1) * chunk : ne;
+    for (int e0 = ch * chunk; e0 < e_end; e0 += SH_NT * 4) {
+        const int e = e0 + tid * 4;
+        int4 v = make_int4(-1, -1, -1, -1);
+        uint32_t f = 0;
+        if (e < e_end) {
+            if (!isg) v = *reinterpret_cast<const int4 *>(src + e);
+            if (share) f = *reinterpret_cast<const uint32_t *>(flag + e);
+        }
+        const int32_t vv[4] = {v.x, v.y, v.z, v.w};
+        int c = 0;                                               // pair entries | plus entries << 16 of this thread
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool g = (f >> (8 * u)) & 1u, d = !isg && e < e_end && vv[u] >= row_base;
+            c += (d && !g ? 1 : 0) + (g ? 0x10000 : 0);
+        }
+        int inc = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const int n = __shfl_up(inc, o); if (lane >= o) inc += n; }
+        __syncthreads();                                         // (wsum of the previous round has been read)
+        if (lane == 63) wsum[wid] = inc;
+        __syncthreads();
+        int wb = 0, tot = 0;
+#pragma unroll
+        for (int q = 0; q < SH_NT / 64; ++q) { if (q < wid) wb += wsum[q]; tot += wsum[q]; }
+        const int excl = wb + inc - c;
+        int jp = run_p + (excl & 0xffff), jg = run_g + (excl >> 16);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool g = (f >> (8 * u)) & 1u, d = !isg && e < e_end && vv[u] >= row_base;
+            if (g) {
+                const int w = plus_pos(jg);
+                if (w >= 0) dst[w] = d ? vv[u] : e + u;
+                ++jg;
+            } else if (d) {
+                if ((jp >> 5) < cap) {
+                    dst[(jp >> 5) * TCELLS + (jp & 31)] = vv[u];
+                    dst[(jp >> 5) * TCELLS + 32 + (jp & 31)] = e + u;
+                }
+                ++jp;
+            }
+        }
+        run_p += tot & 0xffff;
+        run_g += tot >> 16;
+    }
+    if (ch == 0) {
+        const bool use = n_all <= cap && (isg || n_all < nt);
+        if (use && tid < 32) {
+            if (n_pair + tid < n_pt * 32) {                       // padding of the last pair tile: +row 0 - row 0
+                const int j = n_pair + tid;
+                dst[(j >> 5) * TCELLS + (j & 31)] = 0;
+                dst[(j >> 5) * TCELLS + 32 + (j & 31)] = 0;
+            }
+            if (n_g + tid < n_half * 32) dst[plus_pos(n_g + tid)] = 0;      // plus padding: the same number of copies of row 0 in every list
+            for (int t = n_pt + n_full; t < n_all; ++t) dst[t * TCELLS + 32 + tid] = 0;   // the ignored halves (any row in bounds)
+        }
+        if (tid == 0) {
+            info[4 * s] = use ? n_all : 0; info[4 * s + 1] = use ? 1 : 0;
+            info[4 * s + 2] = n_pt; info[4 * s + 3] = n_pt + n_full;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // fused token kernel.  512 threads = 8 waves; persistent over the live list.  A work item ("group") = 8 consecutive live pieces =
 // 64 rows = four 16-row MFMA groups; its pieces may belong to different tiles / scenes, each brings its own 4 x 6 halo.
@@ -1611,6 +1773,29 @@ extern "C" int lvq_bev_scene_pairs(const int32_t *row_src, int batch, int n_tile
         return lvq_launch_status();
     }
     hipLaunchKernelGGL(bt::k_scene_pairs, dim3(batch), dim3(bt::PAIR_NT), 0, lvq_s(stream), row_src, n_tiles, row_base, cap_tiles, pair_src, pair_info);
+    return lvq_launch_status();
+}
+
+// Lists of the shared subtraction (see k_shared_write): list_src [batch + 1, cap_tiles, 64] (entry `batch` = the G list), list_info [batch + 1, 4].
+// Workspace (scratch of the call): 64 n_tiles + 512 (batch + 1) + 512 bytes.
+extern "C" int lvq_bev_shared_lists(const int32_t *row_src, int batch, int n_tiles, int row_base, int cap_tiles, int32_t *list_src, int32_t *list_info,
+                                    void *ws, size_t ws_bytes, lvq_stream_t stream) {
+    if (!row_src || !list_src || !list_info || batch <= 0 || n_tiles <= 0 || cap_tiles <= 0 || row_base < 0) return LVQ_EINVAL;
+    if (((uintptr_t)row_src & 15) || (int64_t)n_tiles * bt::TCELLS > 0x7fffffff || batch > 65534) return LVQ_EUNSUPPORTED;
+    if (cap_tiles < n_tiles) return LVQ_EUNSUPPORTED;            // the G list (<= n_tiles tiles) must always fit: the scenes' lists rely on it
+    const int ne = n_tiles * bt::TCELLS;
+    LvqArena arena(ws, ws_bytes);
+    uint8_t *flag = arena.take<uint8_t>((size_t)ne);
+    int32_t *cnt = arena.take<int32_t>((size_t)(2 * batch + 1) * 64);
+    if (!arena.ok) return LVQ_EWORKSPACE;
+    int64_t chunk = ((int64_t)ne + 63) / 64;
+    chunk = (chunk + 1023) / 1024 * 1024;
+    const int nch = (int)(((int64_t)ne + chunk - 1) / chunk);
+    hipStream_t st = lvq_s(stream);
+    hipLaunchKernelGGL(bt::k_shared_flags, dim3((unsigned)lvq_cdiv(ne, bt::SH_NT * 4)), dim3(bt::SH_NT), 0, st, row_src, batch, ne, row_base, flag);
+    hipLaunchKernelGGL(bt::k_shared_count, dim3(nch, batch), dim3(bt::SH_NT), 0, st, row_src, flag, batch, n_tiles, row_base, (int)chunk, cnt);
+    hipLaunchKernelGGL(bt::k_shared_write, dim3(nch, batch + 1), dim3(bt::SH_NT), 0, st, row_src, flag, batch, n_tiles, row_base, cap_tiles, (int)chunk,
+                       nch, cnt, list_src, list_info);
     return lvq_launch_status();
 }
 

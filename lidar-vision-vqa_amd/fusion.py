@@ -150,17 +150,28 @@ class VATBlock(_HipModule):
 
     def forward_tokens_tiled_signed(self, q2_1: torch.Tensor, qp: BF, totals: torch.Tensor, x_rows: BF, kv: torch.Tensor, row_src: torch.Tensor,
                                     rows_dev: torch.Tensor, B: int, nq: int, n_tiles: int, k_fp16: bool = False,
-                                    stats: Optional[torch.Tensor] = None) -> torch.Tensor:
+                                    stats: Optional[torch.Tensor] = None, totals_k_fp16: int = 0) -> torch.Tensor:
         """forward_tokens_tiled for scene-independent queries: the attention streams each scene's DIRTY rows only (twice: the computed
-        rows added, the table rows of the same cells subtracted from the per-model `totals`), csrc/attention.hip `signed pair stream`."""
+        rows added, the table rows of the same cells subtracted from the per-model `totals`), csrc/attention.hip `signed pair stream`.
+        Batches of three or more scenes subtract the table rows that most of their scenes have dirty once per call (`shared subtraction`,
+        include/lvq.h: lvq_bev_shared_lists); LVQ_NO_SHARED_SUBTRACT=1 keeps the per-scene pair lists.  `totals_k_fp16`: the k_fp16
+        `totals` was computed with."""
         d, h = self.d_model, self.n_heads
         dh = d // h
         hw = n_tiles * 64
         if x_rows is not None:                                  # unfused route: tokens -> K|V GEMM; the fused kernel has filled kv[hw:] already
             ops.linear_live_rows(x_rows, self._w(self.ca.in_proj_weight), self.ca.in_proj_bias, rows_dev, (d, 3 * d), tag="ca_kv_proj", out=kv[hw:])
-        pair_src, pair_info = ops.bev_scene_pairs(row_src, B, n_tiles, hw)
-        o = ops.attention_tiled_signed(qp, kv, row_src, pair_src, pair_info, totals, batch=B, n_heads=h, nq=nq, n_tiles=n_tiles,
-                                       dh=dh, scale=1.0 / math.sqrt(dh), shared_q=True, tag="ca_attn", k_fp16=k_fp16, stats=stats)
+        # The shared lists make a scene's bits depend on the other scenes of its batch (fp32 accumulation order only).  A caller that pins the
+        # KV split (lvq_tuning.attn_nsplit) is asking for bits that do not follow the batch, and keeps the per-scene pair lists.
+        if B >= 3 and not os.environ.get("LVQ_NO_SHARED_SUBTRACT") and not F.get_tuning()["attn_nsplit"]:
+            list_src, list_info = ops.bev_shared_lists(row_src, B, n_tiles, hw)
+            o = ops.attention_tiled_shared(qp, kv, row_src, list_src, list_info, totals, batch=B, n_heads=h, nq=nq, n_tiles=n_tiles, dh=dh,
+                                           scale=1.0 / math.sqrt(dh), totals_k_fp16=totals_k_fp16, tag="ca_attn", k_fp16=k_fp16, stats=stats)
+            pair_info = list_info[:B, :2]                       # (tiles, use) per scene, as the pair lists report them
+        else:
+            pair_src, pair_info = ops.bev_scene_pairs(row_src, B, n_tiles, hw)
+            o = ops.attention_tiled_signed(qp, kv, row_src, pair_src, pair_info, totals, batch=B, n_heads=h, nq=nq, n_tiles=n_tiles,
+                                           dh=dh, scale=1.0 / math.sqrt(dh), shared_q=True, tag="ca_attn", k_fp16=k_fp16, stats=stats)
         q2 = q2_1.unsqueeze(0).expand(B, nq, d).reshape(B * nq, d)
         y, _ = ops.linear(o, self._w(self.ca.out_proj.weight), self.ca.out_proj.bias, residual=q2, out_f32=True, tag="ca_out_proj")
         self._last_pair_info = pair_info                      # device tensor, read by bench / tests only
@@ -653,7 +664,8 @@ class VATLiDAR(_HipModule):
                 if getattr(self, "_guard_stats", None) is None or self._guard_stats.device != dev:
                     object.__setattr__(self, "_guard_stats", torch.zeros(4, dtype=torch.int32, device=dev))
                 q2 = blk.forward_tokens_tiled_signed(q2_1, qp, totals, x_live, table, src, counts[2:], batch, self.n_queries, nt, k_fp16=k16,
-                                                     stats=self._guard_stats)
+                                                     stats=self._guard_stats,
+                                                     totals_k_fp16=(1 if os.environ.get("LVQ_TOTALS_Q16") else 2) if k16 else 0)
                 qps.append(qp[0])
             else:
                 q2, qp_l = blk.forward_tokens_tiled(q2, x_live, table, src, counts[2:], batch, self.n_queries, nt)

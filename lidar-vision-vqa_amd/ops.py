@@ -561,6 +561,43 @@ def attention_tiled_signed(q: BF, kv: torch.Tensor, row_src: torch.Tensor, pair_
     return oh, ol
 
 
+def bev_shared_lists(row_src: torch.Tensor, batch: int, n_tiles: int, row_base: int):
+    """Lists of the shared subtraction (include/lvq.h: lvq_bev_shared_lists) -> (list_src [batch + 1, n_tiles, 64] i32, list_info
+    [batch + 1, 4] i32 = tiles, use flag, first add tile, first ignore tile); entry `batch` is the list of the shared set G."""
+    dev = row_src.device
+    L = F.lib()
+    list_src = torch.empty((batch + 1, n_tiles, 64), dtype=torch.int32, device=dev)
+    list_info = torch.empty((batch + 1, 4), dtype=torch.int32, device=dev)
+    ws = F.workspace(64 * n_tiles + 512 * (batch + 1) + 512, dev, "shared_lists")      # include/lvq.h: lvq_bev_shared_lists
+    rc = L.lvq_bev_shared_lists(F.ptr(row_src), batch, n_tiles, row_base, n_tiles, F.ptr(list_src), F.ptr(list_info), F.ptr(ws), ws.numel(),
+                                F.stream_ptr(dev))
+    F.check(rc, "lvq_bev_shared_lists")
+    return list_src, list_info
+
+
+def attention_tiled_shared(q: BF, kv: torch.Tensor, row_src: torch.Tensor, list_src: torch.Tensor, list_info: torch.Tensor, totals: torch.Tensor, *,
+                           batch: int, n_heads: int, nq: int, n_tiles: int, dh: int, scale: float, totals_k_fp16: int = 0,
+                           tag: Optional[str] = None, k_fp16: bool = False, stats: Optional[torch.Tensor] = None) -> BF:
+    """attention_tiled_signed with the lists of bev_shared_lists: table rows that most scenes of the batch subtract are subtracted once.
+    q BF [nq, d] (one copy for all batches); `totals_k_fp16` = the k_fp16 `totals` was computed with -> BF [batch*nq, d]."""
+    qh, ql = q
+    dev = qh.device
+    d = n_heads * dh
+    oh, ol = _bf_empty((batch * nq, d), dev, ql is not None)
+    L = F.lib()
+    nbytes = int(L.lvq_attention_tiled_signed_workspace_bytes(batch, n_heads, nq, n_tiles, dh))
+    if nbytes == 0:
+        raise F.LvqError(f"attention_tiled_shared: shape (nq={nq}, tiles={n_tiles}, dh={dh}) is not a long-stream shape")
+    ws = F.workspace(nbytes, dev, "attn")
+    with region(tag, dev):
+        rc = L.lvq_attention_bf16_tiled_shared(F.ptr(qh), F.ptr(ql), F.ptr(kv), F.ptr(kv[:, d:]), F.ptr(row_src), F.ptr(list_src), F.ptr(list_info),
+                                               list_src.shape[1], F.ptr(totals), int(totals_k_fp16), batch, n_heads, nq, n_tiles, dh,
+                                               d, dh, 2 * d, dh, nq * d, d, dh, scale, 1 if k_fp16 else 0, F.ptr(oh), F.ptr(ol), F.ptr(stats),
+                                               F.ptr(ws), ws.numel(), F.stream_ptr(dev))
+    F.check(rc, f"lvq_attention_bf16_tiled_shared (B={batch}, H={n_heads}, nq={nq}, tiles={n_tiles})")
+    return oh, ol
+
+
 def stream_guard(q_hi: torch.Tensor, k_rows: torch.Tensor, n_heads: int, scale: float) -> torch.Tensor:
     """Per-model half of the plain-stream guard (include/lvq.h: lvq_stream_guard): q_hi [nq, >= n_heads * 64] bf16, k_rows [nkv, >= n_heads * 64]
     bf16 (row strides = q_hi.stride(0), k_rows.stride(0): column slices of a wider projection are taken as they are) -> g [n_heads, nq] fp32,
