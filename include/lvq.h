@@ -692,6 +692,61 @@ int lvq_deconv2d(const lvq_bf16 *in_hi, const lvq_bf16 *in_lo, int batch, int h,
                  int out_c_total, int out_c_off, lvq_stream_t stream);
 
 /* =====================================================================================
+ * CenterHead post-processing (csrc/center_head.hip): heat maps -> box candidates -> rotated BEV NMS -> per-scene lists
+ * ===================================================================================== */
+
+/* Top-K + decode of centernet_utils.py:155-241 as center_head.py:297-326 calls it, for every (scene, task) in ONE launch.
+ *   maps          [batch, c_total, h, w] fp32: the raw outputs of the tasks' last convs, all tasks side by side in the channels
+ *   task_channels HOST [n_tasks, 6] int32: first channel of center (2), center_z (1), dim (3), rot (2: cos, sin), vel (2, or -1 = none)
+ *                 and hm (n_cls) of each task;  task_n_cls HOST [n_tasks];  class_map HOST [sum n_cls]: the tasks' class-id mappings
+ *                 one behind the other (center_head.py:329).  All three are copied into the kernel's arguments: at most 16 tasks and
+ *                 64 classes in all (else LVQ_EUNSUPPORTED).
+ *   per group g = scene * n_tasks + task: the k largest sigmoid(hm) over n_cls * h * w (class = flat index / (h * w)), descending,
+ *                 EQUAL SCORES TOWARDS THE LOWER FLAT INDEX; dim = exp, heading = atan2(sin, cos), x = (col + center_x) * stride *
+ *                 voxel_xy[0] + range_xy[0] (y alike with the row), each product rounded to fp32 in that order; a candidate stays when
+ *                 limit_range[0..2] <= (x, y, z) <= limit_range[3..5] and score > score_thresh (a negative score_thresh keeps every
+ *                 score: the reference's None); the survivors are compacted in score order.
+ *   outputs       boxes [batch, n_tasks, k, box_dim] fp32 (box_dim 9 = with vel in every task, 7 = in none), scores [batch, n_tasks, k],
+ *                 labels [batch, n_tasks, k] int32 (mapped, 0-based), counts [batch, n_tasks] int32; rows behind a count are zeros.
+ * k <= 1024 (else LVQ_EUNSUPPORTED); k > n_cls * h * w of any task: LVQ_EINVAL (torch.topk raises there), as are NULL operands, non-positive
+ * sizes, a channel range outside c_total and a box_dim that disagrees with the vel channels.  ws below the query: LVQ_EWORKSPACE.  Every
+ * refusal happens before any launch.  One workgroup per group, nothing handed between workgroups; no allocation, stream-ordered.
+ * The query writes *bytes and returns a status like every call (max_cls = the largest n_cls of a task). */
+int lvq_center_decode_workspace_bytes(int batch, int n_tasks, int max_cls, int h, int w, size_t *bytes);
+int lvq_center_decode(const float *maps, int batch, int c_total, int h, int w, int n_tasks, const int32_t *task_channels,
+                      const int32_t *task_n_cls, const int32_t *class_map, int k, int box_dim, int stride, const float *voxel_xy,
+                      const float *range_xy, const float *limit_range, float score_thresh, float *boxes, float *scores, int32_t *labels,
+                      int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* Pairwise rotated BEV IoU of iou3d_nms_utils.py:31-45: boxes_a [n, 7], boxes_b [m, 7] fp32 rows (x, y, z, dx, dy, dz, heading), dx, dy > 0;
+ * iou [n, m] fp32 = area(a ^ b) / max(dx_a dy_a + dx_b dy_b - area, 1e-8).  The area is the exact intersection of the two rotated
+ * rectangles (a's corners in b's frame, clipped against b's four sides, shoelace), in fp32: no corner margin.  One launch, no workspace.
+ * NULL operand or non-positive count: LVQ_EINVAL; n above 262140: LVQ_EUNSUPPORTED. */
+int lvq_boxes_iou_bev(const float *boxes_a, int n, const float *boxes_b, int m, float *iou, lvq_stream_t stream);
+
+/* nms_gpu of iou3d_nms_utils.py:120-135 under class_agnostic_nms (model_nms_utils.py:6-25) for `groups` independent lists in two launches
+ * and no host round trip.  boxes [groups, n_max, box_stride] fp32, box_stride >= 7 (the first seven floats of a row are used), each
+ * group ALREADY in descending score order; counts [groups] int32 on the DEVICE, read by the kernels only, clamped to 0 .. n_max.
+ *   n = min(counts[g], pre_max) rows enter (NMS_PRE_MAXSIZE truncates before NMS); row j is dropped when a kept row i < j has
+ *   iou(i, j) > thresh (strict); keep [groups, post_max] int32 = the kept row numbers ascending, cut at post_max (NMS_POST_MAXSIZE), -1 behind
+ *   keep_count [groups].  Launch 1: one wave per 64 x 64 tile on or above the diagonal writes the suppression words into ws; launch 2:
+ *   one wave per group walks them.  The IoU is lvq_boxes_iou_bev's.
+ * n_max <= 1024 and groups <= 65535 (else LVQ_EUNSUPPORTED); NULL operand, non-positive size, box_stride < 7: LVQ_EINVAL; ws below the
+ * query: LVQ_EWORKSPACE; all before any launch.  The query writes *bytes and returns a status. */
+int lvq_nms_bev_workspace_bytes(int groups, int n_max, size_t *bytes);
+int lvq_nms_bev(const float *boxes, int box_stride, const int32_t *counts, int groups, int n_max, int pre_max, int post_max, float thresh,
+                int32_t *keep, int32_t *keep_count, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* The gather and concatenation of center_head.py:352-363 in one launch: for scene b the kept rows of task 0, then of task 1, ... go to
+ * out_boxes [batch, n_tasks * post_max, box_dim], out_scores [batch, n_tasks * post_max] and out_labels [batch, n_tasks * post_max] int64
+ * (labels + 1: 1-based); out_count [batch] int32 = the scene's total.  boxes / scores / labels are lvq_center_decode's outputs with k
+ * rows per group, keep / keep_count lvq_nms_bev's with groups = batch * n_tasks.  Rows behind out_count are left as they were: the caller
+ * slices.  n_tasks <= 16 (else LVQ_EUNSUPPORTED); NULL operand, non-positive size, box_dim outside {7, 9}: LVQ_EINVAL, before the launch. */
+int lvq_center_collect(const float *boxes, const float *scores, const int32_t *labels, const int32_t *keep, const int32_t *keep_count,
+                       int batch, int n_tasks, int k, int box_dim, int post_max, float *out_boxes, float *out_scores, int64_t *out_labels,
+                       int32_t *out_count, lvq_stream_t stream);
+
+/* =====================================================================================
  * Decode-step runtime
  * ===================================================================================== */
 

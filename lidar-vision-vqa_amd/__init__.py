@@ -4,6 +4,7 @@ Import name: `lidar_vision_vqa_amd` (the root-level shim `lidar_vision_vqa_amd.p
 directory, whose on-disk name carries a hyphen).  Sub-packages:
 
   lidar   voxeliser / VFE / BEV-scatter plugins with the OpenPCDet `batch_dict` protocol
+  dense_head  CenterHead (BEV features -> 3-D boxes: conv stack, top-K decode, rotated BEV NMS) with the reference's module API
   fusion  VATBlock / VATLiDAR / VATVision / VisionAdapter with the reference's nn.Module API
   vision_tower  the SAM ViT image encoder (ImageEncoderViT, build_sam_vit_b) with the reference's nn.Module API
   head    prefix assembly + stand-in decoder head

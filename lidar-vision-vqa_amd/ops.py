@@ -11,6 +11,7 @@ residual x - hi for a split one (see include/lvq.h "Precision modes").  Modes:
 """
 from __future__ import annotations
 
+import ctypes
 import os
 from typing import Optional, Tuple
 
@@ -701,3 +702,91 @@ def linear_ln(a: BF, w: BF, bias: Optional[torch.Tensor], gamma: torch.Tensor, b
                                       k, k, F.ptr(yh), F.ptr(yl), F.stream_ptr(ah.device))
     F.check(rc, f"lvq_gemm_ln_bf16 (m={m}, n={n}, k={k})")
     return yh, yl
+
+
+def _ws_query(fn, what: str, *args) -> int:
+    """A `*_workspace_bytes(..., size_t *bytes)` query that returns a status."""
+    n = ctypes.c_size_t(0)
+    F.check(fn(*args, ctypes.byref(n)), what)
+    return n.value
+
+
+def center_decode(maps: torch.Tensor, task_channels, task_n_cls, class_map, *, k: int, box_dim: int, stride: int, voxel_xy, range_xy,
+                  limit_range, score_thresh: Optional[float], tag: Optional[str] = None):
+    """lvq_center_decode.  maps [B, c_total, H, W] fp32; task_channels: per task the first channel of (center, center_z, dim, rot, vel or
+    -1, hm); task_n_cls and class_map (the tasks' class-id mappings, concatenated) are host lists.  score_thresh None keeps every score.
+    Returns (boxes [B, T, k, box_dim], scores [B, T, k], labels [B, T, k] int32, counts [B, T] int32): candidates in descending score
+    order, equal scores towards the lower flat index, rows behind a count zero."""
+    F.require_cuda(maps)
+    if maps.dim() != 4 or maps.dtype != torch.float32:
+        raise F.LvqError(f"center_decode: expected fp32 [B, C, H, W] maps, got {maps.dtype} {tuple(maps.shape)}")
+    b, c_total, h, w = maps.shape
+    n_tasks, dev = len(task_n_cls), maps.device
+    if len(task_channels) != n_tasks or any(len(r) != 6 for r in task_channels) or len(class_map) != sum(int(c) for c in task_n_cls):
+        raise F.LvqError("center_decode: task_channels is [n_tasks][6], class_map holds sum(task_n_cls) entries")
+    L = F.lib()
+    boxes = torch.empty((b, n_tasks, k, box_dim), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n_tasks, k), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n_tasks, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((b, n_tasks), dtype=torch.int32, device=dev)
+    chans = F.i32x([c for row in task_channels for c in row])
+    args = (F.ptr(maps), b, c_total, h, w, n_tasks, chans, F.i32x(task_n_cls), F.i32x(class_map), k, box_dim, stride, F.f32x(voxel_xy),
+            F.f32x(range_xy), F.f32x(limit_range), -1.0 if score_thresh is None else float(score_thresh), F.ptr(boxes), F.ptr(scores),
+            F.ptr(labels), F.ptr(counts))
+    n = ctypes.c_size_t(0)
+    rc = L.lvq_center_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), h, w, ctypes.byref(n))
+    ws = F.workspace(n.value, dev, "center_head") if rc == F.LVQ_OK else None        # a refused query: the call below names the reason
+    with region(tag, dev):
+        rc = L.lvq_center_decode(*args, F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+    F.check(rc, f"lvq_center_decode (B={b}, {n_tasks} tasks, {h} x {w}, K={k})")
+    return boxes, scores, labels, counts
+
+
+def boxes_iou_bev(boxes_a: torch.Tensor, boxes_b: torch.Tensor) -> torch.Tensor:
+    """lvq_boxes_iou_bev: [N, 7] x [M, 7] fp32 (x, y, z, dx, dy, dz, heading) -> rotated BEV IoU [N, M]."""
+    F.require_cuda(boxes_a, boxes_b)
+    if boxes_a.dim() != 2 or boxes_b.dim() != 2 or boxes_a.shape[1] != 7 or boxes_b.shape[1] != 7 or boxes_a.dtype != torch.float32 or \
+            boxes_b.dtype != torch.float32:
+        raise F.LvqError(f"boxes_iou_bev: expected fp32 [N, 7] and [M, 7], got {tuple(boxes_a.shape)} and {tuple(boxes_b.shape)}")
+    n, m = boxes_a.shape[0], boxes_b.shape[0]
+    out = torch.empty((n, m), dtype=torch.float32, device=boxes_a.device)
+    if n and m:
+        F.check(F.lib().lvq_boxes_iou_bev(F.ptr(boxes_a), n, F.ptr(boxes_b), m, F.ptr(out), F.stream_ptr(out.device)), "lvq_boxes_iou_bev")
+    return out
+
+
+def nms_bev(boxes: torch.Tensor, counts: torch.Tensor, *, thresh: float, pre_max: int, post_max: int, tag: Optional[str] = None):
+    """lvq_nms_bev.  boxes [G, N_max, >= 7] fp32, each group in descending score order; counts [G] int32 on the device.
+    Returns (keep [G, post_max] int32: kept row numbers ascending, -1 behind the count; keep_count [G] int32).  No host read."""
+    F.require_cuda(boxes, counts)
+    if boxes.dim() != 3 or boxes.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != boxes.shape[0]:
+        raise F.LvqError(f"nms_bev: expected fp32 boxes [G, N, >= 7] and int32 counts [G], got {tuple(boxes.shape)} and {tuple(counts.shape)}")
+    g, n_max, stride = boxes.shape
+    dev, L = boxes.device, F.lib()
+    keep = torch.empty((g, post_max), dtype=torch.int32, device=dev)
+    keep_count = torch.empty((g,), dtype=torch.int32, device=dev)
+    ws = F.workspace(_ws_query(L.lvq_nms_bev_workspace_bytes, f"lvq_nms_bev_workspace_bytes ({g} groups of {n_max})", g, n_max), dev,
+                     "center_head_nms")
+    with region(tag, dev):
+        rc = L.lvq_nms_bev(F.ptr(boxes), stride, F.ptr(counts), g, n_max, int(pre_max), int(post_max), float(thresh), F.ptr(keep),
+                           F.ptr(keep_count), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
+    F.check(rc, f"lvq_nms_bev ({g} groups of {n_max})")
+    return keep, keep_count
+
+
+def center_collect(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, keep: torch.Tensor, keep_count: torch.Tensor,
+                   tag: Optional[str] = None):
+    """lvq_center_collect: the kept rows of every scene's tasks in head order -> (boxes [B, T * post_max, D], scores, labels int64
+    1-based, count [B] int32); rows behind a scene's count are not written."""
+    F.require_cuda(boxes, scores, labels, keep, keep_count)
+    b, t, k, d = boxes.shape
+    post_max, dev = keep.shape[-1], boxes.device
+    out_b = torch.empty((b, t * post_max, d), dtype=torch.float32, device=dev)
+    out_s = torch.empty((b, t * post_max), dtype=torch.float32, device=dev)
+    out_l = torch.empty((b, t * post_max), dtype=torch.int64, device=dev)
+    out_n = torch.empty((b,), dtype=torch.int32, device=dev)
+    with region(tag, dev):
+        rc = F.lib().lvq_center_collect(F.ptr(boxes), F.ptr(scores), F.ptr(labels), F.ptr(keep), F.ptr(keep_count), b, t, k, d, post_max,
+                                        F.ptr(out_b), F.ptr(out_s), F.ptr(out_l), F.ptr(out_n), F.stream_ptr(dev))
+    F.check(rc, "lvq_center_collect")
+    return out_b, out_s, out_l, out_n
