@@ -9,7 +9,8 @@
 //   k_nms_walk         second half.  One wave per group walks the rows on the device: the mask never travels to the host.
 //   k_center_collect   center_head.py:352-363.  One workgroup per scene gathers the kept rows of its tasks, in head order.
 //
-// Order of the candidates.  The key is the fp32 score sigmoid(hm) itself (NaN sorts first, as torch.topk has it), descending; equal
+// Order of the candidates.  The key is the fp32 score sigmoid(hm) itself, descending; a NaN of either sign sorts first, as torch.topk has
+// it (all NaNs share one key, so they are ordered like any other tie; they fail `score > thresh` and are kept when there is none); equal
 // scores are taken and ordered towards the LOWER flat index c * H * W + y * W + x, so the result does not depend on how threads were
 // scheduled.  torch.topk leaves the order of equal scores open; the reference's two-stage top-k (per class, then over the classes'
 // winners) selects the same set as this global one whenever the scores around the K-th are distinct.
@@ -42,9 +43,11 @@ struct CenterGeom {
     float stride, vx, vy, rx, ry, lim[6], thresh;
 };
 
-// fp32 bits -> unsigned key with the order of the floats (negative values below positive ones, +NaN on top)
+// fp32 bits -> unsigned key with the order of the floats (negative values below positive ones).  Every NaN, whatever its sign bit and
+// payload, gets the one top key: sigmoid(+NaN) carries the sign bit of -NaN through exp, the add and the divide, and would sort last.
 __device__ __forceinline__ uint32_t key_of(float f) {
     const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float score_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }

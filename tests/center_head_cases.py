@@ -1,8 +1,9 @@
 """Host side (numpy / torch CPU, fp64) of the CenterHead tests: the cases, and restatements written from the module structure and the
 geometry, not from the kernels.
 
-  module cases   MODULE_CASES: two layouts of pcdet/models/dense_heads/center_head.py (nusc: six tasks, ten classes, vel, stride 8;
-                 single: one task, three classes, no vel, stride 4), B = 2, 64 input channels, a 16 x 16 map, K = 32.  Weights come from
+  module cases   MODULE_CASES: three layouts of pcdet/models/dense_heads/center_head.py (nusc: six tasks, ten classes, vel, stride 8;
+                 single: one task, three classes, no vel, stride 4; both on a 16 x 16 map with K = 32; waymo: one task, three classes, no vel,
+                 stride 1, no bias before the norms, BN_EPS 1e-3, a 16 x 24 map with K = 96), B = 2, 64 input channels.  Weights come from
                  synth.seeded_array per state_dict key (conv + ReLU layers rescaled to N(0, 2 / fan_in)); the hm branch's last conv is
                  scaled by `hm_scale` and its bias set to `hm_bias`, so that a few dozen peaks per scene stand clear of SCORE_THRESH.
   head_maps      the conv stack in fp64: F.conv2d, BatchNorm folded with the case's eps, ReLU, bias
@@ -45,13 +46,20 @@ DIM_SCALE, DIM_BIAS = 0.3, -0.6                  # log-sizes about N(-0.6, 0.35)
 BN_EPS = 1e-5                                    # center_head.py:74: the default of model_cfg.get('BN_EPS', 1e-5)
 
 
-def head_cfg(heads, vel, stride, k, num_conv=2, limit=(-6.0, -10.0, -10.0, 6.0, 10.0, 10.0), pre=1000, post=83, nms_type="nms_gpu", **extra):
+def head_cfg(heads, vel, stride, k, num_conv=2, limit=(-6.0, -10.0, -10.0, 6.0, 10.0, 10.0), pre=1000, post=83, nms_type="nms_gpu",
+             bias_before_norm=True, nms_thresh=NMS_THRESH, score_thresh=SCORE_THRESH, **extra):
+    """bias_before_norm None leaves USE_BIAS_BEFORE_NORM out (the class default, False); score_thresh None leaves SCORE_THRESH out."""
     names = ["center", "center_z", "dim", "rot"] + (["vel"] if vel else [])
-    return Cfg(CLASS_NAMES_EACH_HEAD=[list(h) for h in heads], SHARED_CONV_CHANNEL=64, USE_BIAS_BEFORE_NORM=True, NUM_HM_CONV=num_conv,
-               SEPARATE_HEAD_CFG=Cfg(HEAD_ORDER=names, HEAD_DICT=Cfg({n: Cfg(out_channels=BRANCH_WIDTH[n], num_conv=num_conv) for n in names})),
-               TARGET_ASSIGNER_CONFIG=Cfg(FEATURE_MAP_STRIDE=stride),
-               POST_PROCESSING=Cfg(SCORE_THRESH=SCORE_THRESH, POST_CENTER_LIMIT_RANGE=list(limit), MAX_OBJ_PER_SAMPLE=k,
-                                   NMS_CONFIG=Cfg(NMS_TYPE=nms_type, NMS_THRESH=NMS_THRESH, NMS_PRE_MAXSIZE=pre, NMS_POST_MAXSIZE=post)), **extra)
+    post_cfg = Cfg(SCORE_THRESH=score_thresh, POST_CENTER_LIMIT_RANGE=list(limit), MAX_OBJ_PER_SAMPLE=k,
+                   NMS_CONFIG=Cfg(NMS_TYPE=nms_type, NMS_THRESH=nms_thresh, NMS_PRE_MAXSIZE=pre, NMS_POST_MAXSIZE=post))
+    cfg = Cfg(CLASS_NAMES_EACH_HEAD=[list(h) for h in heads], SHARED_CONV_CHANNEL=64, USE_BIAS_BEFORE_NORM=bias_before_norm, NUM_HM_CONV=num_conv,
+              SEPARATE_HEAD_CFG=Cfg(HEAD_ORDER=names, HEAD_DICT=Cfg({n: Cfg(out_channels=BRANCH_WIDTH[n], num_conv=num_conv) for n in names})),
+              TARGET_ASSIGNER_CONFIG=Cfg(FEATURE_MAP_STRIDE=stride), POST_PROCESSING=post_cfg, **extra)
+    if bias_before_norm is None:
+        del cfg["USE_BIAS_BEFORE_NORM"]
+    if score_thresh is None:
+        del post_cfg["SCORE_THRESH"]
+    return cfg
 
 
 # name -> what the constructor and a forward need.  A 16 x 16 map of 0.8 m cells spans the 12.8 m range; the limit range cuts its outer 0.4 m
@@ -64,12 +72,19 @@ MODULE_CASES = {
     "single": dict(heads=[["Car", "Pedestrian", "Cyclist"]], vel=False, stride=4, k=32, class_names=["Car", "Pedestrian", "Cyclist"],
                    input_channels=64, shape=(2, 64, 16, 16), voxel_size=[0.2, 0.2, 0.2], point_cloud_range=[-6.4, -6.4, -5.0, 6.4, 6.4, 3.0],
                    grid_size=[64, 64, 40], wseed=72, xseed=172, hm_scale=2.5, hm_bias=-2.0),
+    # the Waymo layout of the reference's configurations: no USE_BIAS_BEFORE_NORM key (the class default: convs in front of a norm have
+    # no bias), BN_EPS 1e-3, stride 1 (pillars), NMS at 0.7 with 4096 / 500, no vel.  K = 96 on a 16 x 24 map of 0.8 m cells: more than 64
+    # survivors per scene, so the NMS mask has two words.  Classes of one cell share its box, so NMS at 0.7 still removes candidates.
+    "waymo": dict(heads=[["Vehicle", "Pedestrian", "Cyclist"]], vel=False, stride=1, k=96, class_names=["Vehicle", "Pedestrian", "Cyclist"],
+                  input_channels=64, shape=(2, 64, 16, 24), voxel_size=[0.8, 0.8, 0.2], point_cloud_range=[-9.6, -6.4, -5.0, 9.6, 6.4, 3.0],
+                  grid_size=[24, 16, 40], wseed=74, xseed=7, hm_scale=2.5, hm_bias=-2.0,
+                  cfg=dict(bias_before_norm=None, nms_thresh=0.7, pre=4096, post=500, limit=(-9.2, -10.0, -10.0, 9.2, 10.0, 10.0), BN_EPS=1e-3)),
 }
 
 
 def case_cfg(name, **kw):
     c = MODULE_CASES[name]
-    return head_cfg(c["heads"], c["vel"], c["stride"], c["k"], **kw)
+    return head_cfg(c["heads"], c["vel"], c["stride"], c["k"], **dict(c.get("cfg", {}), **kw))
 
 
 def case_input(name, xseed=None):
@@ -148,8 +163,9 @@ def _bn_relu(x, sd, prefix, eps):
     return torch.relu(x * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1))
 
 
-def head_maps(cfg, sd, x, eps=BN_EPS):
-    """spatial_features_2d [B, C, H, W] -> one dict {branch: fp64 [B, width, H, W]} per task."""
+def head_maps(cfg, sd, x, eps=None):
+    """spatial_features_2d [B, C, H, W] -> one dict {branch: fp64 [B, width, H, W]} per task.  eps: the configuration's BN_EPS."""
+    eps = cfg.get("BN_EPS", BN_EPS) if eps is None else eps
     x = _bn_relu(_conv(_d(x), sd, "shared_conv.0"), sd, "shared_conv.1", eps)
     out = []
     for i in range(len(cfg.CLASS_NAMES_EACH_HEAD)):
@@ -169,7 +185,8 @@ def head_maps(cfg, sd, x, eps=BN_EPS):
 # --------------------------------------------------------------------------------------------------------------------------------
 def scores32(hm):
     """sigmoid of fp32 logits, evaluated in fp64 and rounded once to fp32 (what a correctly rounded fp32 sigmoid returns)."""
-    return (1.0 / (1.0 + np.exp(-np.asarray(hm, np.float64)))).astype(np.float32)
+    with np.errstate(over="ignore"):                                        # a -inf logit: exp(+inf), score 0
+        return (1.0 / (1.0 + np.exp(-np.asarray(hm, np.float64)))).astype(np.float32)
 
 
 def decode_ref(task, k, stride, voxel_xy, range_xy, limit, thresh, class_ids, extra=8):
@@ -181,7 +198,9 @@ def decode_ref(task, k, stride, voxel_xy, range_xy, limit, thresh, class_ids, ex
     out = []
     for s in range(b):
         sc = scores32(hm[s]).reshape(-1)
-        order = np.lexsort((np.arange(sc.size), -sc.astype(np.float64)))       # descending score, ties towards the lower flat index
+        # descending score, ties towards the lower flat index; a NaN of either sign comes before every number, as torch.topk has it
+        with np.errstate(invalid="ignore"):
+            order = np.lexsort((np.arange(sc.size), -np.where(np.isnan(sc), np.inf, sc.astype(np.float64))))
         top = order[:k]
         cls, pix = top // (h * w), top % (h * w)
         ys, xs = pix // w, pix % w
@@ -197,7 +216,8 @@ def decode_ref(task, k, stride, voxel_xy, range_xy, limit, thresh, class_ids, ex
         lim = np.asarray(limit, np.float64)
         mask = (boxes[:, :3] >= lim[:3]).all(1) & (boxes[:, :3] <= lim[3:]).all(1)
         if thresh is not None:
-            mask &= sc[top] > np.float32(thresh)
+            with np.errstate(invalid="ignore"):
+                mask &= sc[top] > np.float32(thresh)                            # False for a NaN
         out.append(dict(boxes=boxes[mask], scores=sc[top][mask], labels=np.asarray(class_ids)[cls][mask], flat=top[mask],
                         cand_scores=sc[order[:min(k + extra, sc.size)]], cand_boxes=boxes))
     return out
@@ -341,7 +361,7 @@ def head_final(cfg, class_names, maps, stride, voxel_size, point_cloud_range):
     for i, heads in enumerate(cfg.CLASS_NAMES_EACH_HEAD):
         ids = [class_names.index(x) for x in heads if x in class_names]
         dec = decode_ref(maps[i], post.MAX_OBJ_PER_SAMPLE, stride, voxel_size[:2], point_cloud_range[:2], post.POST_CENTER_LIMIT_RANGE,
-                         post.SCORE_THRESH, ids)
+                         post.get("SCORE_THRESH"), ids)
         pre.append(dec)
         for s, d in enumerate(dec):
             keep, m = greedy_nms(d["boxes"], nms.NMS_THRESH, nms.NMS_PRE_MAXSIZE, nms.NMS_POST_MAXSIZE)
@@ -368,10 +388,28 @@ def case_ref(name):
     return maps64, pre, final, near
 
 
+# name -> (the MODULE_CASES entry it varies, the configuration changes, the input's seed: the first from 1 that meets the margin conditions)
+MODULE_VARIANTS = {
+    "num_conv1": ("single", dict(num_conv=1), 1),                 # the last convs read the shared features: no block-diagonal weight
+    "no_score_thresh": ("single", dict(score_thresh=None), 4),    # SCORE_THRESH absent: all K candidates inside the limits reach NMS
+}
+
+
+@functools.lru_cache(maxsize=None)
+def variant_ref(name):
+    """(cfg, state, x, maps64, pre, final, near) of a MODULE_VARIANTS entry, from the restatement alone."""
+    base, kw, xseed = MODULE_VARIANTS[name]
+    c, cfg = MODULE_CASES[base], case_cfg(base, **kw)
+    sd, x = state(cfg, c["input_channels"], c["wseed"], c["hm_scale"], c["hm_bias"]), case_input(base, xseed)
+    maps64 = head_maps(cfg, sd, x)
+    pre, final, near = head_final(cfg, c["class_names"], f32_maps(maps64), c["stride"], c["voxel_size"], c["point_cloud_range"])
+    return cfg, sd, x, maps64, pre, final, near
+
+
 def module_margins(cfg, pre, near):
     """(K-th to (K + 1)-th score gap, |score - SCORE_THRESH|, |iou - NMS_THRESH|, |centre - limit|): the smallest over tasks and scenes."""
     post = cfg.POST_PROCESSING
-    m = [decode_margins(d, post.MAX_OBJ_PER_SAMPLE, post.POST_CENTER_LIMIT_RANGE, post.SCORE_THRESH) for task in pre for d in task]
+    m = [decode_margins(d, post.MAX_OBJ_PER_SAMPLE, post.POST_CENTER_LIMIT_RANGE, post.get("SCORE_THRESH")) for task in pre for d in task]
     return min(x[1] for x in m), min(x[2] for x in m), near, min(x[3] for x in m)
 
 
@@ -389,11 +427,24 @@ DECODE_CASES = {
     "large_no_vel": (2, 40, 48, 500, [1, 2], False, 4, 424),
 }
 DECODE_VOXEL = [0.1, 0.1]
+# Further cases of the same generator, run by tests/test_gpu_center_head_edges.py (seeds: the first from 201 at which the margin conditions hold
+# for every K the case is run with).  k_sizes: one map of n = 2 x 32 x 32 = 2048 distinct scores for K in K_SIZES (the bitonic sort over P = 2, 2,
+# 4, 1024, 1024; at 1024 every thread of the sort is busy); k_is_n: K = n = 1024, every cell a winner; stride1: the pillar layout.
+DECODE_EDGE_CASES = {
+    "k_sizes": (2, 32, 32, 1024, [2], False, 4, 212),
+    "k_is_n": (2, 32, 32, 1024, [1], False, 4, 204),
+    "stride1": (2, 12, 20, 32, [1], False, 1, 205),
+}
+K_SIZES = (1, 2, 3, 1023, 1024)
+
+
+def decode_spec(name):
+    return DECODE_CASES[name] if name in DECODE_CASES else DECODE_EDGE_CASES[name]
 
 
 def decode_geometry(name):
     """(voxel_xy, range_xy, limit): the range spans the grid, the limit range cuts 0.4 cells off every side."""
-    _, h, w, _, _, _, stride, _ = DECODE_CASES[name]
+    _, h, w, _, _, _, stride, _ = decode_spec(name)
     cell = stride * DECODE_VOXEL[0]
     rx, ry = -0.5 * w * cell, -0.5 * h * cell
     return DECODE_VOXEL, [rx, ry], [rx + 0.4 * cell, ry + 0.4 * cell, -3.0, -rx - 0.4 * cell, -ry - 0.4 * cell, 3.0]
@@ -402,7 +453,7 @@ def decode_geometry(name):
 @functools.lru_cache(maxsize=None)
 def decode_case(name):
     """(maps [B, c_total, H, W] fp32 with the tasks' branches side by side, task_channels, class ids per task, per task {branch: view})."""
-    b, h, w, _, classes, vel, _, seed = DECODE_CASES[name]
+    b, h, w, _, classes, vel, _, seed = decode_spec(name)
     rng = np.random.default_rng(seed)
     names = ["center", "center_z", "dim", "rot"] + (["vel"] if vel else []) + ["hm"]
     c_total = sum(sum(BRANCH_WIDTH.get(n, 0) for n in names) + nc for nc in classes)
@@ -479,22 +530,301 @@ NMS_COUNTS, NMS_N_MAX, NMS_SEED, NMS_MARGIN = [0, 1, 63, 64, 65, 130, 500], 500,
 
 
 @functools.lru_cache(maxsize=None)
-def nms_case():
-    """boxes [7, 500, 7] fp32 in "score order" (the row number), counts, and per group the fp64 IoU matrix of its rows.  Boxes come in
-    clusters of about six, so that a good half is suppressed; a box is drawn again (the stream of one seeded generator) while its fp64 IoU
-    with any earlier box of its group lies within 0.02 of the threshold."""
-    rng = np.random.default_rng(NMS_SEED)
-    boxes = np.zeros((len(NMS_COUNTS), NMS_N_MAX, 7), np.float32)
+def nms_case(thresh=NMS_THRESH, counts=tuple(NMS_COUNTS), n_max=NMS_N_MAX, margin=NMS_MARGIN, seed=NMS_SEED, jitter=None):
+    """boxes [G, n_max, 7] fp32 in "score order" (the row number), counts, and per group the fp64 IoU matrix of its rows.  Boxes come in
+    clusters of about six, so that a good half is suppressed at 0.2; a box is drawn again (the stream of one seeded generator) while its
+    fp64 IoU with any earlier box of its group lies within `margin` of the threshold.  Only earlier boxes whose circumscribed circle
+    meets the candidate's are clipped: the others have an IoU of exactly zero, which the condition accepts whenever thresh >= margin.
+    jitter (centre, relative size, heading): every cluster has one prototype box and its members differ from it by at most that much,
+    so that a fair share of the pairs overlaps by more than a high threshold; None draws size and heading freely (the 0.2 cases)."""
+    assert thresh >= margin
+    rng = np.random.default_rng(seed)
+    boxes = np.zeros((len(counts), n_max, 7), np.float32)
     ious = []
-    for g, n in enumerate(NMS_COUNTS):
+    for g, n in enumerate(counts):
         centres = rng.uniform(-50, 50, (max(1, n // 6), 2))
+        protos = random_boxes(rng, len(centres), lo=1.0, hi=5.0) if jitter is not None else None
         for i in range(n):
             while True:
-                cand = random_boxes(rng, 1, lo=1.0, hi=5.0)[0]
-                cand[:2] = (centres[rng.integers(len(centres))] + rng.uniform(-2.5, 2.5, 2)).astype(np.float32)
-                if i == 0 or np.abs(iou_pairs(np.repeat(cand[None], i, 0), boxes[g, :i]) - NMS_THRESH).min() >= NMS_MARGIN:
+                if jitter is None:
+                    cand = random_boxes(rng, 1, lo=1.0, hi=5.0)[0]
+                    cand[:2] = (centres[rng.integers(len(centres))] + rng.uniform(-2.5, 2.5, 2)).astype(np.float32)
+                else:
+                    c = rng.integers(len(centres))
+                    cand = protos[c].copy()
+                    cand[:2] = (centres[c] + rng.uniform(-jitter[0], jitter[0], 2)).astype(np.float32)
+                    cand[3:5] *= (1.0 + rng.uniform(-jitter[1], jitter[1], 2)).astype(np.float32)
+                    cand[6] += np.float32(rng.uniform(-jitter[2], jitter[2]))
+                prev = boxes[g, :i]
+                reach = 0.5 * np.hypot(cand[3], cand[4]) + 0.5 * np.hypot(prev[:, 3], prev[:, 4])
+                hit = np.nonzero(np.hypot(prev[:, 0] - cand[0], prev[:, 1] - cand[1]) <= reach)[0]
+                if hit.size == 0 or np.abs(iou_pairs(np.repeat(cand[None], hit.size, 0), prev[hit]) - thresh).min() >= margin:
                     break
             boxes[g, i] = cand
         ious.append(iou_matrix(boxes[g, :n], boxes[g, :n]))
     boxes.setflags(write=False)
-    return boxes, list(NMS_COUNTS), ious
+    return boxes, list(counts), ious
+
+
+# (thresh, counts, n_max, margin, jitter) of the further NMS cases.  wide: 16 mask words, a full and a 63-row last chunk, counts on both sides
+# of 15 chunks.  high / low: the thresholds of the reference's Waymo (0.7) and ONCE (0.01) configurations; at 0.01 a margin of 0.02 cannot be
+# kept (disjoint boxes sit at IoU 0), the condition is |iou - 0.01| >= 0.005: every fp64 IoU below 0.005 or above 0.015, five times the
+# kernel's IoU bar of 1e-3.  full: three full groups for the count clamps.
+NMS_EDGE_CASES = {
+    "wide": (NMS_THRESH, (1024, 1023, 961, 960, 0), 1024, NMS_MARGIN, None),
+    "high": (0.7, (130, 65, 64, 1), 130, NMS_MARGIN, (0.25, 0.08, 0.08)),
+    "low": (0.01, (130, 65, 64, 1), 130, 0.005, None),
+    "full": (NMS_THRESH, (130, 130, 130), 130, NMS_MARGIN, None),
+}
+
+
+NMS_WIDE_GOLDEN = "center_head_nms_wide.npz"     # tools/make_center_head_nms_wide.py: drawing the 3968 boxes of "wide" takes about 6 s
+
+
+def nms_edge_generate(name):
+    thresh, counts, n_max, margin, jitter = NMS_EDGE_CASES[name]
+    return nms_case(thresh, counts, n_max, margin, NMS_SEED + 1 + list(NMS_EDGE_CASES).index(name), jitter)
+
+
+@functools.lru_cache(maxsize=None)
+def nms_edge_case(name):
+    """(boxes, counts, fp64 IoU matrices) of an NMS_EDGE_CASES entry; the boxes of "wide" come from the committed fixture."""
+    if name != "wide":
+        return nms_edge_generate(name)
+    import os
+    boxes = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", NMS_WIDE_GOLDEN))["boxes"]
+    counts = list(NMS_EDGE_CASES[name][1])
+    boxes.setflags(write=False)
+    return boxes, counts, [iou_matrix(boxes[g, :n], boxes[g, :n]) for g, n in enumerate(counts)]
+
+
+NMS_CHAIN_ROWS = dict(a=10, b=70, c=700, a2=20, b2=1000, c2=1010)
+
+
+@functools.lru_cache(maxsize=None)
+def nms_chain_case():
+    """One group of 1024 axis-aligned boxes, no randomness: unit squares on a 32 x 32 grid of 3 m (all disjoint), and two triples of
+    2 x 2 squares shifted by 0.8 m each: IoU(A, B) = IoU(B, C) = 2.4 / 5.6 = 0.43 and IoU(A, C) = 0.8 / 7.2 = 0.11 around the threshold of 0.2.
+    A suppresses B, and C survives because B is gone: rows 10 (chunk 0), 70 (chunk 1), 700 (chunk 10); the second triple has its suppressor in
+    chunk 0 (row 20) and victim and survivor in chunk 15 (rows 1000, 1010).  Returns (boxes [1, 1024, 7], the rows that are kept)."""
+    n = 1024
+    boxes = np.zeros((1, n, 7), np.float32)
+    r = np.arange(n)
+    boxes[0, :, 0], boxes[0, :, 1], boxes[0, :, 3:6] = 3.0 * (r % 32), 3.0 * (r // 32), 1.0
+    rows = NMS_CHAIN_ROWS
+    for k, (names, y) in enumerate(((("a", "b", "c"), -50.0), (("a2", "b2", "c2"), -80.0))):
+        for j, name in enumerate(names):
+            boxes[0, rows[name]] = _box(-100.0 + 0.8 * j, y, 2.0, 2.0, 0.0)
+    boxes.setflags(write=False)
+    return boxes, [i for i in range(n) if i not in (rows["b"], rows["b2"])]
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# kernel cases: IoU edges
+# --------------------------------------------------------------------------------------------------------------------------------
+N_IOU_CLOSED_FORM_BASE = len(IOU_CLOSED_FORM)
+IOU_FAR_OFFSET = (4000.0, -3000.0)
+# At that offset an fp32 coordinate has an ulp of 2^-12 = 2.44e-4 m, so a corner computed in scene coordinates is off by up to half of it
+# and an overlap extent (the difference of two corners) by up to one ulp.  For the 2 x 2 half-overlap pair, inter = w h with w = 1, h = 2:
+# d(inter) <= h dw + w dh = 3 ulps = 7.3e-4, and IoU = inter / (8 - inter) has the slope 8 / (8 - inter)^2 = 2 / 9: 1.6e-4, rounded up.
+IOU_FAR_BAR = 2e-4
+IOU_CLOSED_FORM += [
+    (_box(0.0, 0.0, 0.0, 2.0, 0.3), _box(0.2, 0.1, 4.0, 2.0, 0.0), 0.0),                            # zero width against a normal box
+    (_box(0.2, 0.1, 4.0, 2.0, 0.0), _box(0.0, 0.0, 2.0, 0.0, 0.3), 0.0),                            # and as the clipping box
+    (_box(1.0, 2.0, 0.0, 0.0, 0.5), _box(1.0, 2.0, 0.0, 0.0, 0.5), 0.0),                            # identical zero-area boxes: 0, not NaN
+    (_box(-3.0, 4.0, 0.05, 20.0, 0.2), _box(-3.0, 4.0, 0.05, 20.0, 0.2 + np.pi / 2), 0.0025 / (2.0 - 0.0025)),      # thin boxes crossed: the
+    (_box(-3.0, 4.0, 0.05, 20.0, 0.2), _box(-3.0, 4.0, 0.05, 20.0, 0.2 + np.pi / 6), 0.005 / (2.0 - 0.005)),        # rhombus 0.05^2 / sin(angle)
+    (_box(IOU_FAR_OFFSET[0], IOU_FAR_OFFSET[1], 2.0, 2.0, 0.0), _box(IOU_FAR_OFFSET[0] + 1.0, IOU_FAR_OFFSET[1], 2.0, 2.0, 0.0), 1.0 / 3.0),
+    (_box(7.0, -7.0, 1e-3, 1e-3, 0.9), _box(7.0, -7.0, 1e-3, 1e-3, 0.9), 1.0),                      # a 1 mm box against its copy
+]
+IOU_FAR_PAIR = N_IOU_CLOSED_FORM_BASE + 5
+# The thin crossed pairs have an IoU of 1.25e-3 and 2.5e-3, which the absolute bar of 1e-3 hardly sees: they get an absolute bar of 1e-5 of their
+# own (under 1 % of the value).  The rhombus' corners come from fp32 sines of headings near 1.77 and 0.72: a relative error of a few 1e-7 in
+# each extent, so 1e-5 leaves two orders of magnitude.
+IOU_THIN_PAIRS, IOU_THIN_BAR = (N_IOU_CLOSED_FORM_BASE + 3, N_IOU_CLOSED_FORM_BASE + 4), 1e-5
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# kernel cases: decode with ties (the radix select's plateau route), NaN, infinities, the sizes of K, the limits
+# --------------------------------------------------------------------------------------------------------------------------------
+LADDER = np.arange(-8.0, 8.25, 0.25)             # 65 logits whose scores are far more than 64 ulps apart, in the kernel and in scores32 alike
+SATURATED = np.array([20.0, 25.0, 40.0, 80.0])   # 1 / (1 + exp(-x)) is exactly 1.0f for each, in fp32 and rounded from fp64
+PLATEAU = 2.0                                    # the plateau's logit; the 23 ladder levels above it are 2.25 .. 7.75
+WIDE_LIMIT = [-1e3, -1e3, -1e3, 1e3, 1e3, 1e3]
+
+# name -> (H, W, K, classes per task, score_thresh, layout).  Two tasks with different n_cls: the workgroups differ in n and in chunk.
+TIE_CASES = {
+    "plateau_straddles_k": (24, 30, 64, [2, 1], SCORE_THRESH, ("plateau", 23, 200)),
+    "plateau_chunk3": (31, 33, 500, [3, 1], SCORE_THRESH, ("plateau", 23, 700)),
+    "plateau_fills_exactly": (24, 30, 64, [2, 1], SCORE_THRESH, ("plateau", 23, 41)),
+    "saturated": (24, 30, 64, [2, 1], SCORE_THRESH, ("saturated", 100)),
+    "all_equal_chunked": (32, 32, 1024, [2, 1], SCORE_THRESH, ("constant",)),
+    "zeros_at_the_bottom": (24, 30, 64, [2, 1], None, ("zeros", 40)),
+}
+TIE_STRIDE, TIE_VOXEL = 4, [0.125, 0.125]        # cells of 0.5 m from the origin: x = col / 2, y = row / 2, exact in fp32
+
+
+def _plateau_cells(rng, n, count, chunk, scene):
+    """`count` flat indices: 0 and n - 1, runs of 2 chunk + 1 neighbours (several equal keys inside one thread's range), singles.  Scene 0
+    spreads them over the map; scene 1 keeps all but index 0 in the upper half, so that whole waves of threads count nothing."""
+    lo = 1 if scene == 0 or count > n // 4 else n // 2
+    cells = {0, n - 1}
+    while len(cells) < count - count // 4:
+        start = int(rng.integers(lo, n - 2 * chunk - 1))
+        cells.update(range(start, start + 2 * chunk + 1))
+    while len(cells) < count:
+        cells.add(int(rng.integers(lo, n)))
+    cells = np.array(sorted(cells))
+    extra = len(cells) - count                   # a run may overshoot: drop the lowest cells behind index 0
+    return np.delete(cells, np.arange(1, 1 + extra))
+
+
+def _tie_logits(rng, n, k, layout, scene):
+    chunk = -(-n // 1024)
+    kind = layout[0]
+    if kind == "constant":
+        return np.full(n, 1.0)
+    hm = rng.choice(LADDER[LADDER < PLATEAU - 1.0], n)                          # the background: ladder levels below the plateau, ties included
+    if kind == "plateau":
+        _, above, count = layout
+        count = min(count, n - above - 8)
+        cells = _plateau_cells(rng, n, count, chunk, scene)
+        hm[cells] = PLATEAU
+        free = np.setdiff1d(np.arange(n), cells)
+        hm[rng.choice(free, above, replace=False)] = LADDER[LADDER > PLATEAU][:above]
+    elif kind == "saturated":
+        cells = _plateau_cells(rng, n, layout[1], chunk, scene)
+        hm[cells] = rng.choice(SATURATED, len(cells))
+        hm[cells[1::7]] = np.inf                                                # +inf joins the class: score exactly 1
+    elif kind == "zeros":
+        hm[:] = -np.inf
+        hm[rng.choice(np.arange(1, n - 1), layout[1], replace=False)] = LADDER[-layout[1]:]
+    return hm
+
+
+@functools.lru_cache(maxsize=None)
+def tie_case(name):
+    """(maps [2, c_total, H, W] fp32, task_channels, class ids per task, per task {branch: view}).  The centre branch is zero and the class
+    mapping is a permutation, so (x, y, label) of an output row names its flat index (tie_flat)."""
+    h, w, k, classes, _, layout = TIE_CASES[name]
+    rng = np.random.default_rng(500 + list(TIE_CASES).index(name))
+    c_total = sum(8 + nc for nc in classes)
+    maps = np.zeros((2, c_total, h, w), np.float32)
+    chans, tasks, ids, c0, cls0 = [], [], [], 0, 0
+    for nc in classes:
+        maps[:, c0 + 2:c0 + 8] = rng.standard_normal((2, 6, h, w)) * 0.7
+        for s in range(2):
+            maps[s, c0 + 8:c0 + 8 + nc] = _tie_logits(rng, nc * h * w, k, layout, s).reshape(nc, h, w)
+        task = dict(center=maps[:, c0:c0 + 2], center_z=maps[:, c0 + 2:c0 + 3], dim=maps[:, c0 + 3:c0 + 6], rot=maps[:, c0 + 6:c0 + 8],
+                    hm=maps[:, c0 + 8:c0 + 8 + nc])
+        chans.append([c0, c0 + 2, c0 + 3, c0 + 6, -1, c0 + 8])
+        tasks.append(task)
+        ids.append(list(range(cls0 + nc - 1, cls0 - 1, -1)))
+        c0, cls0 = c0 + 8 + nc, cls0 + nc
+    maps.setflags(write=False)
+    return maps, chans, ids, tasks
+
+
+def tie_flat(boxes, labels, ids, h, w):
+    """Output rows -> flat indices c * H * W + y * W + x, from x = col / 2, y = row / 2 and the permutation `ids` of one task."""
+    cls = np.array([list(ids).index(int(v)) for v in labels], np.int64)
+    col, row = np.rint(np.asarray(boxes)[:, 0] * 2).astype(np.int64), np.rint(np.asarray(boxes)[:, 1] * 2).astype(np.int64)
+    return cls * h * w + row * w + col
+
+
+def select_stats(hm, k):
+    """What the radix select meets on one heat map [n_cls, H, W]: (keys strictly above the K-th score, keys equal to it, how many of those
+    belong to the K winners, the range length per thread)."""
+    sc = scores32(hm).reshape(-1)
+    kth = np.sort(sc)[::-1][k - 1]
+    above, eq = int((sc > kth).sum()), int((sc == kth).sum())
+    return above, eq, k - above, -(-sc.size // 1024)
+
+
+def tie_separation(cand_scores):
+    """The smallest gap, in ulps of the larger score, between neighbours of the candidates' scores that are not bit-equal (NaNs left out)."""
+    cs = cand_scores[~np.isnan(cand_scores)]
+    gaps = -np.diff(cs.astype(np.float64))
+    ulps = gaps / np.spacing(cs[:-1]).astype(np.float64)
+    return float(ulps[gaps > 0].min()) if (gaps > 0).any() else np.inf
+
+
+NAN_BITS = (0x7fc00000, 0xffc00000)
+NAN_CELLS = (27, 57, 118, 121, 170, 209)         # inner cells of the 12 x 20 map, signs alternating
+NAN_LIFT = 1.0
+
+
+@functools.lru_cache(maxsize=None)
+def nan_case():
+    """decode_case("small_k32") with six heat-map cells of either scene overwritten by NaNs, three of each sign bit.  Scene 0's logits are
+    raised by NAN_LIFT first, so that more than K finite scores pass SCORE_THRESH: with the threshold, a select that put the NaNs last would
+    keep K finite candidates where K - 6 are right."""
+    maps, chans, ids, _ = decode_case("small_k32")
+    maps = maps.copy()
+    maps[0, chans[0][5]] += np.float32(NAN_LIFT)
+    hm = maps[:, chans[0][5]].reshape(2, -1).view(np.uint32)
+    for j, cell in enumerate(NAN_CELLS):
+        hm[:, cell] = NAN_BITS[j % 2]
+    maps.setflags(write=False)
+    names = ("center", "center_z", "dim", "rot", "vel", "hm")
+    task = {n: maps[:, c:c + (1 if n == "hm" else BRANCH_WIDTH[n])] for n, c in zip(names, chans[0]) if c >= 0}
+    return maps, chans, ids, [task]
+
+
+def without_nans(dec, n_nan):
+    """One scene of decode_ref with its first n_nan candidates (the NaNs) taken off, for decode_margins."""
+    assert np.isnan(dec["cand_scores"][:n_nan]).all() and not np.isnan(dec["cand_scores"][n_nan:]).any()
+    return dict(dec, cand_scores=dec["cand_scores"][n_nan:], cand_boxes=dec["cand_boxes"][n_nan:])
+
+
+DECODE_NO_THRESH = "small_k32"                   # the DECODE_CASES entry that is also run with score_thresh=None
+
+
+@functools.lru_cache(maxsize=None)
+def limit_case():
+    """Centres exactly on the limit range.  Cells of 0.5 m from (-4, -4) on a 16 x 16 map and a zero centre branch: x = col / 2 - 4 and
+    y = row / 2 - 4 are exact in fp32.  The limits lie on cell centres: x in [-2, 2.5] (columns 4 .. 13), y in [-1.5, 3] (rows 5 .. 14),
+    z in [-3, 3].  Candidates sit on each limit, on two corners and one cell outside each; two more have center_z exactly on -3 and 3 and two
+    the next fp32 outside.  Returns (maps [2, 9, 16, 16], task_channels, ids, tasks, limit, range_xy, {(row, col): kept?})."""
+    h = w = 16
+    maps = np.zeros((2, 9, h, w), np.float32)
+    maps[:, 3:6], maps[:, 6], maps[:, 8] = -0.5, 1.0, -6.0
+    cells = {(8, 4): True, (8, 3): False, (8, 13): True, (8, 14): False, (5, 8): True, (4, 8): False, (14, 8): True, (15, 8): False,
+             (5, 4): True, (14, 13): True, (4, 3): False, (15, 14): False, (9, 9): True, (10, 9): True, (9, 10): False, (10, 10): False}
+    z = {(9, 9): -3.0, (10, 9): 3.0, (9, 10): np.nextafter(np.float32(-3.0), np.float32(-4.0)), (10, 10): np.nextafter(np.float32(3.0), np.float32(4.0))}
+    for s in range(2):
+        levels = LADDER[-len(cells):] if s == 0 else LADDER[-len(cells):][::-1]
+        for (cell, _), v in zip(cells.items(), levels):
+            maps[s, 8][cell] = v
+    for cell, v in z.items():
+        maps[:, 2][(slice(None),) + cell] = v
+    maps.setflags(write=False)
+    task = dict(center=maps[:, 0:2], center_z=maps[:, 2:3], dim=maps[:, 3:6], rot=maps[:, 6:8], hm=maps[:, 8:9])
+    return maps, [[0, 2, 3, 6, -1, 8]], [[0]], [task], [-2.0, -1.5, -3.0, 2.5, 3.0, 3.0], [-4.0, -4.0], cells
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# kernel cases: collect
+# --------------------------------------------------------------------------------------------------------------------------------
+COLLECT_KEEP_COUNTS = [[[0, 5, 0], [3, 0, 2]], [[0, 0, 0], [0, 0, 0]], [[5, 1, 0], [2, 70, 3]]]      # [run][scene][task]; the last clamps at post_max = 1
+
+
+def collect_case(box_dim, post_max, keep_count, k=70, seed=601):
+    """Hand-made inputs of lvq_center_collect for B = 2, T = 3: (boxes, scores, labels, keep) and the expected (boxes, scores, labels,
+    count) per scene: the kept rows in head order, then keep order; labels + 1."""
+    rng = np.random.default_rng(seed + box_dim + post_max)
+    b, t = 2, 3
+    boxes = rng.standard_normal((b, t, k, box_dim)).astype(np.float32)
+    scores = rng.random((b, t, k)).astype(np.float32)
+    labels = rng.integers(0, 10, (b, t, k)).astype(np.int32)
+    keep = np.full((b, t, post_max), -1, np.int32)
+    want = []
+    for s in range(b):
+        rows = []
+        for ti in range(t):
+            n = max(0, min(int(keep_count[s][ti]), post_max))
+            keep[s, ti, :min(post_max, k)] = np.sort(rng.permutation(k)[:min(post_max, k)])    # valid rows behind the count, too: the count decides
+            rows += [(ti, int(r)) for r in keep[s, ti, :n]]
+        want.append((np.array([boxes[s, ti, r] for ti, r in rows], np.float32).reshape(-1, box_dim),
+                     np.array([scores[s, ti, r] for ti, r in rows], np.float32), np.array([labels[s, ti, r] + 1 for ti, r in rows], np.int64)))
+    return boxes, scores, labels, keep, want

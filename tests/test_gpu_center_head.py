@@ -28,7 +28,8 @@ DEV = "cuda:0"
 BAR = 1e-3
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 # max |maps - restatement| / max(1, max|restatement|) over every branch of every task in the plain bf16 form, measured on the MI355X
-PLAIN_MEASURED = {"nusc": 6.79e-3, "single": 5.36e-3}       # (bf16x3 on the same cases: 1.35e-5, 1.16e-5)
+PLAIN_MEASURED = {"nusc": 6.79e-3, "single": 5.36e-3, "waymo": 5.15e-3}    # (bf16x3 on the same cases: 1.35e-5, 1.16e-5, 9.81e-6)
+# waymo: measured 2026-10-20 on [2, 64, 16, 24], K = 96, stride 1, BN_EPS 1e-3, no bias before the norm
 
 
 def t(a):

@@ -26,6 +26,7 @@ values are center_head_cases.case_state(name), loaded with strict=True -- 5 MB o
 Printed on the last run (survivors before NMS -> kept, per scene; margins: K-th gap, |score - 0.1|, |iou - 0.2|, |centre - limit|):
     nusc     scene 0: 184 -> 170   scene 1: 179 -> 169   margins 1.42e-03 2.06e-01 2.05e-02 1.86e-02   292 KiB
     single   scene 0: 30 -> 29   scene 1: 32 -> 29   margins 4.26e-03 6.72e-01 8.58e-02 1.44e-01   147 KiB
+    waymo    scene 0: 96 -> 90   scene 1: 92 -> 88   margins 1.51e-03 5.42e-01 1.60e-01 1.93e-02   223 KiB   (|iou - 0.7|)
 """
 from __future__ import annotations
 
