@@ -641,6 +641,30 @@ int lvq_sparse_conv(const float *feat, int64_t n_in, int c_in, const int32_t *nb
                     const lvq_bf16 *w_hi, const lvq_bf16 *w_lo, int c_out, const float *bias, const float *scale, const float *shift,
                     const float *residual, int relu, float *out, lvq_stream_t stream);
 
+/* The branch convs of VoxelNeXtHead (voxelnext_head.py:13-47; csrc/sparse_head.hip): every branch of every task in ONE launch over the n
+ * active rows.  A branch is SubMConv2d(128, 128, k) + BatchNorm1d + ReLU followed by SubMConv2d(128, out, 1, bias).
+ *   feat        [n, 128] fp32;  nbr [n, k_vol] int32 from lvq_sparse_conv_rules(subm, 2-D), k_vol = 9, or k_vol = 1 where nbr may be NULL
+ *               ("row i reads row i").  An entry outside [0, n) reads as absent.
+ *   task_n_br   HOST [n_tasks]: branches of each task (1 .. 8, each <= br_stride);  chan_owner HOST [n_tasks, task_c]: the branch that owns
+ *               output channel c of the task, negative = nobody (task_c <= 16; channels task_c .. 15 have no owner either)
+ *   w_hi, w_lo  [n_tasks][br_stride][k_vol][128][128] bf16: per (task, branch) exactly what lvq_sparse_conv_pack_weights writes for
+ *               (c_out 128, k_vol, c_in 128); w_lo == NULL is the plain form, else hi*hi + hi*lo + lo*hi.  Slots of branches a task
+ *               does not have are not read.
+ *   scale/shift [n_tasks][br_stride][128] fp32, the folded BatchNorm (a conv bias folded by the caller: shift' = bias * scale + shift)
+ *   w_last      [n_tasks][16][128] fp32, bias [n_tasks][16]: output channel c reads the intermediate of the branch that owns c
+ *   num_conv    2: as above.  1: there is no first conv, the last conv reads feat itself (nbr, w_hi, w_lo, scale, shift are ignored).
+ *   out         CHANNEL-major [16 * n_tasks, n] fp32: channel 16 t + c of row i at (16 t + c) * n + i.  The decode scans hm over all rows
+ *               and gathers the box channels of K rows only.  Channels nobody owns are written as zeros.
+ * Order: lvq_sparse_conv's -- offsets ascending, channels ascending inside an offset, fp32 accumulation, no atomics; the last conv is an
+ * fp32 fmaf chain over the 128 intermediate channels in ascending order, then + bias.  A row's bits depend on its own neighbours only:
+ * not on its tile, its position, n or the other scenes.  The 128-wide intermediate stays on chip.
+ * c_in != 128, k_vol outside {1, 9}, more than 16 tasks, more than 8 branches or 16 output channels in a task, misaligned (16 bytes)
+ * feat / w_hi / w_lo, n >= 2^31: LVQ_EUNSUPPORTED.  NULL operands (nbr with k_vol = 9), non-positive sizes, an owner >= the task's branch
+ * count, num_conv outside {1, 2}: LVQ_EINVAL.  Every refusal comes before any launch; no allocation, no workspace, stream-ordered. */
+int lvq_sparse_head(const float *feat, int64_t n, int c_in, const int32_t *nbr, int k_vol, int n_tasks, const int32_t *task_n_br, int br_stride,
+                    const int32_t *chan_owner, int task_c, int num_conv, const lvq_bf16 *w_hi, const lvq_bf16 *w_lo, const float *scale,
+                    const float *shift, const float *w_last, const float *bias, float *out, lvq_stream_t stream);
+
 /* =====================================================================================
  * Dense 2-D BEV backbone (csrc/conv2d.hip): the layers of BaseBEVBackbone / BaseBEVBackboneV1 and of PillarRes18BackBone8x's dense conv5
  * ===================================================================================== */
@@ -745,6 +769,31 @@ int lvq_nms_bev(const float *boxes, int box_stride, const int32_t *counts, int g
 int lvq_center_collect(const float *boxes, const float *scores, const int32_t *labels, const int32_t *keep, const int32_t *keep_count,
                        int batch, int n_tasks, int k, int box_dim, int post_max, float *out_boxes, float *out_scores, int64_t *out_labels,
                        int32_t *out_count, lvq_stream_t stream);
+
+/* Top-K + decode of centernet_utils.py:243-354 (decode_bbox_from_voxels_nuscenes, as voxelnext_head.py:443-456 calls it) over the rows of
+ * a sparse tensor, for every (scene, task) in ONE launch.  The selection, the sort, the masks and the compaction are lvq_center_decode's.
+ *   head          CHANNEL-major [c_total, n_rows] fp32: lvq_sparse_head's output (c_total = 16 * n_tasks there)
+ *   indices       [n_rows, 3] int32 (b, y, x).  The candidates of a scene are the rows with b == scene, in stored order; they need not be
+ *                 contiguous.  A row whose b is outside [0, batch) takes no part.
+ *   task_channels / task_n_cls / class_map, k, box_dim, stride, voxel_xy, range_xy, limit_range, score_thresh: as for lvq_center_decode.
+ *   per group g = scene * n_tasks + task: the min(k, n_cls * n_b) largest sigmoid(hm) of the scene's n_b rows, descending, EQUAL SCORES
+ *                 TOWARDS THE LOWER (class, stored row) PAIR (the lower flat index of the reference's [n_cls, n_b] matrix); NaNs first;
+ *                 dim = exp, heading = atan2(sin, cos), x = (col + center_x) * stride * voxel_xy[0] + range_xy[0] (y alike with the row),
+ *                 each product rounded to fp32 in that order; limit-range and score masks; compaction in score order.
+ *   outputs       exactly lvq_center_decode's: boxes [batch, n_tasks, k, box_dim], scores, labels int32 (mapped, 0-based), counts
+ *                 [batch, n_tasks]; rows behind a count are zeros.  lvq_nms_bev and lvq_center_collect take them unchanged.
+ * ONE DELIBERATE DIFFERENCE from the reference: when a scene has fewer than k rows, _topk_1d still computes class = ind // k on an
+ * [n_cls, n_b] matrix, which gives wrong classes, and when n_cls * n_b < k its torch.stack / .view(batch, k) raise.  Here the class is the
+ * matrix row the candidate came from and the count is what there is (a scene without rows: count 0, no row is read).  With n_b >= k in
+ * every scene the two agree.
+ * k <= 1024, at most 16 tasks and 64 classes, max_cls * n_rows < 2^31 (else LVQ_EUNSUPPORTED); NULL operands, non-positive batch or k, a
+ * channel range outside c_total, a box_dim that disagrees with the vel channels: LVQ_EINVAL; ws below the query: LVQ_EWORKSPACE.  Every
+ * refusal happens before the launch.  One workgroup per group, nothing handed between workgroups; no allocation, stream-ordered. */
+int lvq_voxel_decode_workspace_bytes(int batch, int n_tasks, int max_cls, int64_t n_rows, size_t *bytes);
+int lvq_voxel_decode(const float *head, const int32_t *indices, int64_t n_rows, int batch, int c_total, int n_tasks,
+                     const int32_t *task_channels, const int32_t *task_n_cls, const int32_t *class_map, int k, int box_dim, int stride,
+                     const float *voxel_xy, const float *range_xy, const float *limit_range, float score_thresh, float *boxes, float *scores,
+                     int32_t *labels, int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
 /* =====================================================================================
  * Decode-step runtime

@@ -5,6 +5,8 @@ directory, whose on-disk name carries a hyphen).  Sub-packages:
 
   lidar   voxeliser / VFE / BEV-scatter plugins with the OpenPCDet `batch_dict` protocol
   dense_head  CenterHead (BEV features -> 3-D boxes: conv stack, top-K decode, rotated BEV NMS) with the reference's module API
+  sparse_head VoxelNeXtHead (the sparse BEV rows of VoxelResBackBone8xVoxelNeXt -> 3-D boxes: fused branch convs, top-K over rows) and the
+              registry of both heads, dense_heads_all
   fusion  VATBlock / VATLiDAR / VATVision / VisionAdapter with the reference's nn.Module API
   vision_tower  the SAM ViT image encoder (ImageEncoderViT, build_sam_vit_b) with the reference's nn.Module API
   head    prefix assembly + stand-in decoder head

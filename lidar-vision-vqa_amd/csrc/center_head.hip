@@ -3,6 +3,13 @@
 //   k_center_decode    centernet_utils.py:155-241.  One workgroup of 1024 threads per (scene, task): a 4 x 8-bit radix select of the K-th
 //                      largest fp32 score over n_cls * H * W, a bitonic sort of the K winners in LDS, the box arithmetic, the masks and
 //                      an order-keeping compaction.  Nothing is handed between workgroups.
+//   k_voxel_decode     centernet_utils.py:243-354 (VoxelNeXtHead): the same selection, sort, masks and compaction (select_sort, decode_box, box_stays,
+//                      compact_store are shared, not copied) over the ROWS of a sparse tensor: the candidates of a scene are the rows
+//                      whose batch index is the scene's, in stored order and not necessarily contiguous; y and x come from the rows'
+//                      own indices.  One deliberate difference from the reference: when a scene has fewer than K rows, _topk_1d still
+//                      computes class = ind // K on an [n_cls, n_b] matrix, which gives wrong classes, and when n_cls * n_b < K its
+//                      torch.stack / .view(batch, K) raise.  Here the class is the matrix row the candidate came from and the count is
+//                      what there is; with n_b >= K in every scene the two agree.
 //   k_boxes_iou_bev    iou3d_nms_utils.py:31-45.  One thread per (a, b) pair.
 //   k_nms_mask         iou3d_nms_utils.py:120-135, first half.  One wave per 64 x 64 tile on or above the diagonal: a lane holds a
 //                      column box, the rows are looped, __ballot(iou > thresh) is the row's 64-bit word.
@@ -52,17 +59,27 @@ __device__ __forceinline__ uint32_t key_of(float f) {
 }
 __device__ __forceinline__ float score_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
+// LDS of the selection, shared by k_center_decode and k_voxel_decode
+struct SelectLds {
+    uint64_t buf[MAX_K];
+    uint32_t hist[256], scan[2][256];
+    uint32_t sel_bin, sel_above, sel_cnt, ncand;
+    uint32_t wcnt[DEC_THREADS / 64];
+};
+
 // histogram of byte `shift` of the keys that agree with `prefix` above it.  Neighbouring candidates mostly fall into one bin, so a thread
-// counts a run in a register and touches the LDS counter once per run.
-template <bool FIRST>
-__device__ void radix_hist(const float *hm, uint32_t *keys, int n, uint32_t prefix, int shift, uint32_t *hist) {
+// counts a run in a register and touches the LDS counter once per run.  key_at(i) is the key of flat index i, or 0 for an index that is
+// no candidate (SPARSE only: key_of never returns 0, the lowest key is -inf's 0x007fffff).
+template <bool FIRST, bool SPARSE, class KeyAt>
+__device__ void radix_hist(KeyAt key_at, uint32_t *keys, int n, uint32_t prefix, int shift, uint32_t *hist) {
     int run_bin = -1;
     uint32_t run = 0;
     const uint32_t hi_mask = shift == 24 ? 0u : ~((1u << (shift + 8)) - 1u);
     for (int i = threadIdx.x; i < n; i += DEC_THREADS) {
         uint32_t k;
-        if (FIRST) { k = key_of(1.0f / (1.0f + expf(-hm[i]))); keys[i] = k; }
+        if (FIRST) { k = key_at(i); keys[i] = k; }
         else k = keys[i];
+        if (SPARSE && k == 0u) continue;
         if ((k & hi_mask) != prefix) continue;
         const int bin = (int)((k >> shift) & 255u);
         if (bin != run_bin) {
@@ -74,57 +91,49 @@ __device__ void radix_hist(const float *hm, uint32_t *keys, int n, uint32_t pref
     if (run) atomicAdd(&hist[run_bin], run);
 }
 
-__global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__restrict__ maps, int c_total, int h, int w, int n_tasks,
-                                                                CenterTasks tk, CenterGeom gm, int K, int box_dim,
-                                                                float *__restrict__ boxes, float *__restrict__ scores,
-                                                                int32_t *__restrict__ labels, int32_t *__restrict__ counts,
-                                                                uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
-    __shared__ uint64_t buf[MAX_K];
-    __shared__ uint32_t hist[256], scan[2][256];
-    __shared__ uint32_t sel_bin, sel_above, sel_cnt, ncand;
-    __shared__ uint32_t wcnt[DEC_THREADS / 64];
-    const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
-    const int64_t hw = (int64_t)h * w;
-    const int n = (int)(tk.n_cls[t] * hw);
-    const float *scene = maps + (int64_t)b * c_total * hw;
-    const float *hm = scene + (int64_t)tk.off[t][5] * hw;
-    uint32_t *keys = keys_ws + (int64_t)g * keys_pitch;
-
+// The K largest keys of key_at(0 .. n - 1), K >= 1 and at most the number of candidates, into s.buf[0 .. K - 1] as (key << 32 | ~index),
+// descending: a 4 x 8-bit radix select of the K-th key, equal keys towards the lower flat index, then a bitonic sort.  keys [n] is the
+// group's scratch in global memory.  Every thread of the workgroup calls it.
+template <bool SPARSE, class KeyAt>
+__device__ void select_sort(SelectLds &s, KeyAt key_at, uint32_t *keys, int n, int K) {
+    uint64_t *buf = s.buf;
+    uint32_t *hist = s.hist, *wcnt = s.wcnt;
+    const int tid = threadIdx.x;
     // ---- the K-th largest key: four passes of 8 bits, most significant first
     uint32_t prefix = 0, need = (uint32_t)K;
     for (int pass = 0; pass < 4; ++pass) {
         const int shift = 24 - 8 * pass;
         if (tid < 256) hist[tid] = 0;
         __syncthreads();
-        if (pass == 0) radix_hist<true>(hm, keys, n, prefix, shift, hist);
-        else radix_hist<false>(hm, keys, n, prefix, shift, hist);
+        if (pass == 0) radix_hist<true, SPARSE>(key_at, keys, n, prefix, shift, hist);
+        else radix_hist<false, SPARSE>(key_at, keys, n, prefix, shift, hist);
         __syncthreads();
         // suffix sums over the 256 bins (Hillis-Steele, 8 steps)
-        if (tid < 256) scan[0][tid] = hist[tid];
+        if (tid < 256) s.scan[0][tid] = hist[tid];
         __syncthreads();
         int cur = 0;
         for (int d = 1; d < 256; d <<= 1) {
-            if (tid < 256) scan[cur ^ 1][tid] = scan[cur][tid] + (tid + d < 256 ? scan[cur][tid + d] : 0u);
+            if (tid < 256) s.scan[cur ^ 1][tid] = s.scan[cur][tid] + (tid + d < 256 ? s.scan[cur][tid + d] : 0u);
             __syncthreads();
             cur ^= 1;
         }
         if (tid < 256) {
-            const uint32_t incl = scan[cur][tid], above = incl - hist[tid];
-            if (above < need && incl >= need) { sel_bin = (uint32_t)tid; sel_above = above; sel_cnt = hist[tid]; }
+            const uint32_t incl = s.scan[cur][tid], above = incl - hist[tid];
+            if (above < need && incl >= need) { s.sel_bin = (uint32_t)tid; s.sel_above = above; s.sel_cnt = hist[tid]; }
         }
         __syncthreads();
-        prefix |= sel_bin << shift;
-        need -= sel_above;
+        prefix |= s.sel_bin << shift;
+        need -= s.sel_above;
         __syncthreads();
     }
-    const uint32_t T = prefix, eq_cnt = sel_cnt;       // `need` of the eq_cnt keys equal to T belong to the K winners
-    if (tid == 0) ncand = 0;
+    const uint32_t T = prefix, eq_cnt = s.sel_cnt;     // `need` of the eq_cnt keys equal to T belong to the K winners
+    if (tid == 0) s.ncand = 0;
     __syncthreads();
     const bool all_equal = need == eq_cnt;
     for (int i = tid; i < n; i += DEC_THREADS) {
         const uint32_t k = keys[i];
         if (k > T || (all_equal && k == T)) {
-            const uint32_t slot = atomicAdd(&ncand, 1u);
+            const uint32_t slot = atomicAdd(&s.ncand, 1u);
             if (slot < (uint32_t)MAX_K) buf[slot] = ((uint64_t)k << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
         }
     }
@@ -146,7 +155,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__re
         }
         for (int i = lo; i < hi && before < need; ++i)
             if (keys[i] == T) {
-                const uint32_t slot = atomicAdd(&ncand, 1u);
+                const uint32_t slot = atomicAdd(&s.ncand, 1u);
                 if (slot < (uint32_t)MAX_K) buf[slot] = ((uint64_t)T << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
                 ++before;
             }
@@ -167,30 +176,31 @@ __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__re
             }
             __syncthreads();
         }
-    // ---- decode, mask, compact (centernet_utils.py:184-221)
-    bool keep = false;
-    float bx[9];
-    float sc = 0.f;
-    int label = 0;
-    if (tid < K) {
-        const uint64_t e = buf[tid];
-        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
-        sc = score_of((uint32_t)(e >> 32));
-        const int cls = (int)(idx / (uint32_t)hw), pix = (int)(idx - (uint32_t)cls * (uint32_t)hw);
-        const int y = pix / w, x = pix - y * w;
-        const int *off = tk.off[t];
-        auto ch = [&](int c) { return scene[(int64_t)c * hw + pix]; };
-        bx[0] = ((float)x + ch(off[0])) * gm.stride * gm.vx + gm.rx;
-        bx[1] = ((float)y + ch(off[0] + 1)) * gm.stride * gm.vy + gm.ry;
-        bx[2] = ch(off[1]);
-        for (int d = 0; d < 3; ++d) bx[3 + d] = expf(ch(off[2] + d));
-        bx[6] = atan2f(ch(off[3] + 1), ch(off[3]));            // rot[:, 0] is the cosine, rot[:, 1] the sine
-        bx[7] = bx[8] = 0.f;
-        if (box_dim == 9) { bx[7] = ch(off[4]); bx[8] = ch(off[4] + 1); }
-        keep = bx[0] >= gm.lim[0] && bx[1] >= gm.lim[1] && bx[2] >= gm.lim[2] && bx[0] <= gm.lim[3] && bx[1] <= gm.lim[4] &&
-               bx[2] <= gm.lim[5] && (gm.thresh < 0.f || sc > gm.thresh);
-        label = tk.cls_map[tk.map_off[t] + cls];
-    }
+}
+
+// the box of a candidate at cell (x, y); ch(c) reads channel c at the candidate (centernet_utils.py:184-212 / 310-319)
+template <class Ch>
+__device__ __forceinline__ void decode_box(Ch ch, int x, int y, const int *off, const CenterGeom &gm, int box_dim, float *bx) {
+    bx[0] = ((float)x + ch(off[0])) * gm.stride * gm.vx + gm.rx;
+    bx[1] = ((float)y + ch(off[0] + 1)) * gm.stride * gm.vy + gm.ry;
+    bx[2] = ch(off[1]);
+    for (int d = 0; d < 3; ++d) bx[3 + d] = expf(ch(off[2] + d));
+    bx[6] = atan2f(ch(off[3] + 1), ch(off[3]));                // rot[:, 0] is the cosine, rot[:, 1] the sine
+    bx[7] = bx[8] = 0.f;
+    if (box_dim == 9) { bx[7] = ch(off[4]); bx[8] = ch(off[4] + 1); }
+}
+
+// masks of centernet_utils.py:214-221 / 332-336
+__device__ __forceinline__ bool box_stays(const float *bx, float sc, const CenterGeom &gm) {
+    return bx[0] >= gm.lim[0] && bx[1] >= gm.lim[1] && bx[2] >= gm.lim[2] && bx[0] <= gm.lim[3] && bx[1] <= gm.lim[4] && bx[2] <= gm.lim[5] &&
+           (gm.thresh < 0.f || sc > gm.thresh);
+}
+
+// order-keeping compaction of the kept candidates of group g (thread tid holds candidate tid) into rows g * K ..; rows behind the count
+// are zeroed, counts[g] is written.  Every thread of the workgroup calls it.
+__device__ void compact_store(uint32_t *wcnt, bool keep, const float *bx, float sc, int label, int g, int K, int box_dim,
+                              float *__restrict__ boxes, float *__restrict__ scores, int32_t *__restrict__ labels, int32_t *__restrict__ counts) {
+    const int tid = threadIdx.x;
     const uint64_t bal = __ballot(keep);
     const int lane = tid & 63, wave = tid >> 6;
     if (lane == 0) wcnt[wave] = (uint32_t)__popcll(bal);
@@ -209,6 +219,80 @@ __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__re
         labels[row0 + tid] = 0;
     }
     if (tid == 0) counts[g] = (int32_t)total;
+}
+
+__global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__restrict__ maps, int c_total, int h, int w, int n_tasks,
+                                                                CenterTasks tk, CenterGeom gm, int K, int box_dim,
+                                                                float *__restrict__ boxes, float *__restrict__ scores,
+                                                                int32_t *__restrict__ labels, int32_t *__restrict__ counts,
+                                                                uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
+    __shared__ SelectLds s;
+    const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
+    const int64_t hw = (int64_t)h * w;
+    const int n = (int)(tk.n_cls[t] * hw);
+    const float *scene = maps + (int64_t)b * c_total * hw;
+    const float *hm = scene + (int64_t)tk.off[t][5] * hw;
+    select_sort<false>(s, [hm](int i) { return key_of(1.0f / (1.0f + expf(-hm[i]))); }, keys_ws + (int64_t)g * keys_pitch, n, K);
+    // ---- decode, mask, compact (centernet_utils.py:184-221)
+    bool keep = false;
+    float bx[9];
+    float sc = 0.f;
+    int label = 0;
+    if (tid < K) {
+        const uint64_t e = s.buf[tid];
+        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
+        sc = score_of((uint32_t)(e >> 32));
+        const int cls = (int)(idx / (uint32_t)hw), pix = (int)(idx - (uint32_t)cls * (uint32_t)hw);
+        const int y = pix / w, x = pix - y * w;
+        decode_box([&](int c) { return scene[(int64_t)c * hw + pix]; }, x, y, tk.off[t], gm, box_dim, bx);
+        keep = box_stays(bx, sc, gm);
+        label = tk.cls_map[tk.map_off[t] + cls];
+    }
+    compact_store(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
+}
+
+// centernet_utils.py:243-354 over rows: the candidates of scene b are the rows with indices[:, 0] == b, flat index = class * n + stored row,
+// so equal scores go towards the lower (class, row) pair.  head is channel-major [c_total, n] (lvq_sparse_head's output).
+__global__ __launch_bounds__(DEC_THREADS) void k_voxel_decode(const float *__restrict__ head, const int32_t *__restrict__ indices, int n_rows,
+                                                               int n_tasks, CenterTasks tk, CenterGeom gm, int K, int box_dim,
+                                                               float *__restrict__ boxes, float *__restrict__ scores,
+                                                               int32_t *__restrict__ labels, int32_t *__restrict__ counts,
+                                                               uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
+    __shared__ SelectLds s;
+    const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
+    const int n_cls = tk.n_cls[t];
+    const float *hm = head + (int64_t)tk.off[t][5] * n_rows;
+    // ---- the scene's row count n_b; K_eff = min(K, n_cls * n_b)
+    if (tid == 0) s.ncand = 0;
+    __syncthreads();
+    uint32_t mine = 0;
+    for (int i = tid; i < n_rows; i += DEC_THREADS) mine += indices[3 * (int64_t)i] == b;
+    for (int d = 32; d > 0; d >>= 1) mine += __shfl_down(mine, d);
+    if ((tid & 63) == 0 && mine) atomicAdd(&s.ncand, mine);
+    __syncthreads();
+    const int64_t cand = (int64_t)n_cls * s.ncand;
+    const int k_eff = (int)(cand < K ? cand : K);
+    __syncthreads();
+    if (k_eff > 0)                                               // (workgroup-uniform)
+        select_sort<true>(s, [=](int i) {
+            const int row = i % n_rows;
+            return indices[3 * (int64_t)row] == b ? key_of(1.0f / (1.0f + expf(-hm[i]))) : 0u;
+        }, keys_ws + (int64_t)g * keys_pitch, n_cls * n_rows, k_eff);
+    bool keep = false;
+    float bx[9];
+    float sc = 0.f;
+    int label = 0;
+    if (tid < k_eff) {
+        const uint64_t e = s.buf[tid];
+        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
+        sc = score_of((uint32_t)(e >> 32));
+        const int cls = (int)(idx / (uint32_t)n_rows), row = (int)(idx - (uint32_t)cls * (uint32_t)n_rows);
+        const int y = indices[3 * (int64_t)row + 1], x = indices[3 * (int64_t)row + 2];
+        decode_box([&](int c) { return head[(int64_t)c * n_rows + row]; }, x, y, tk.off[t], gm, box_dim, bx);
+        keep = box_stays(bx, sc, gm);
+        label = tk.cls_map[tk.map_off[t] + cls];
+    }
+    compact_store(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -441,6 +525,63 @@ extern "C" int lvq_center_decode(const float *maps, int batch, int c_total, int 
     if (!arena.ok) return LVQ_EWORKSPACE;
     hipLaunchKernelGGL(k_center_decode, dim3((unsigned)(batch * n_tasks)), dim3(DEC_THREADS), 0, lvq_s(stream), maps, c_total, h, w, n_tasks, tk,
                        gm, k, box_dim, boxes, scores, labels, counts, keys, pitch);
+    return lvq_launch_status();
+}
+
+extern "C" int lvq_voxel_decode_workspace_bytes(int batch, int n_tasks, int max_cls, int64_t n_rows, size_t *bytes) {
+    if (!bytes || batch <= 0 || n_tasks <= 0 || max_cls <= 0 || n_rows < 0) return LVQ_EINVAL;
+    const int64_t n = (int64_t)max_cls * n_rows;
+    if (n >= (1ll << 31) || n_tasks > MAX_TASKS || max_cls > MAX_CLASSES) return LVQ_EUNSUPPORTED;
+    LvqSizer s;
+    s.take<uint32_t>((size_t)batch * n_tasks * (size_t)lvq_align((size_t)n * 4 + 4, 256) / 4);
+    *bytes = s.total();
+    return LVQ_OK;
+}
+
+extern "C" int lvq_voxel_decode(const float *head, const int32_t *indices, int64_t n_rows, int batch, int c_total, int n_tasks,
+                                const int32_t *task_channels, const int32_t *task_n_cls, const int32_t *class_map, int k, int box_dim,
+                                int stride, const float *voxel_xy, const float *range_xy, const float *limit_range, float score_thresh,
+                                float *boxes, float *scores, int32_t *labels, int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream) {
+    if (!task_channels || !task_n_cls || !class_map || !voxel_xy || !range_xy || !limit_range || !boxes || !scores || !labels || !counts ||
+        batch <= 0 || c_total <= 0 || n_rows < 0 || n_tasks <= 0 || k <= 0 || stride <= 0 || (box_dim != 7 && box_dim != 9) ||
+        (n_rows > 0 && (!head || !indices)))
+        return LVQ_EINVAL;
+    if (n_tasks > MAX_TASKS) return LVQ_EUNSUPPORTED;
+    CenterTasks tk = {};
+    const int width[6] = {2, 1, 3, 2, 2, 0};
+    int max_cls = 0, total_cls = 0;
+    for (int t = 0; t < n_tasks; ++t) {
+        const int nc = task_n_cls[t];
+        if (nc <= 0) return LVQ_EINVAL;
+        if (total_cls + nc > MAX_CLASSES) return LVQ_EUNSUPPORTED;
+        for (int f = 0; f < 6; ++f) {
+            const int c = task_channels[t * 6 + f], wd = f == 5 ? nc : width[f];
+            if (f == 4 ? (box_dim == 9) != (c >= 0) : c < 0) return LVQ_EINVAL; // vel in every task of a 9-wide box, in none of a 7-wide one
+            if (c >= 0 && c + wd > c_total) return LVQ_EINVAL;
+            tk.off[t][f] = c;
+        }
+        tk.n_cls[t] = nc;
+        tk.map_off[t] = total_cls;
+        for (int c = 0; c < nc; ++c) tk.cls_map[total_cls + c] = class_map[total_cls + c];
+        total_cls += nc;
+        max_cls = nc > max_cls ? nc : max_cls;
+    }
+    if (k > MAX_K) return LVQ_EUNSUPPORTED;
+    size_t need = 0;
+    const int rc = lvq_voxel_decode_workspace_bytes(batch, n_tasks, max_cls, n_rows, &need);
+    if (rc != LVQ_OK) return rc;
+    if (!ws || ws_bytes < need) return LVQ_EWORKSPACE;
+    CenterGeom gm;
+    gm.stride = (float)stride; gm.vx = voxel_xy[0]; gm.vy = voxel_xy[1]; gm.rx = range_xy[0]; gm.ry = range_xy[1];
+    for (int i = 0; i < 6; ++i) gm.lim[i] = limit_range[i];
+    gm.thresh = score_thresh;
+    const int64_t pitch = (int64_t)(lvq_align((size_t)max_cls * n_rows * 4 + 4, 256) / 4);
+    LvqArena arena(ws, ws_bytes);
+    uint32_t *keys = arena.take<uint32_t>((size_t)batch * n_tasks * pitch);
+    if (!arena.ok) return LVQ_EWORKSPACE;
+    // (n_rows = 0: every group finds no candidate, reads no row and writes its zeros and its count)
+    hipLaunchKernelGGL(k_voxel_decode, dim3((unsigned)(batch * n_tasks)), dim3(DEC_THREADS), 0, lvq_s(stream), head, indices, (int)n_rows, n_tasks,
+                       tk, gm, k, box_dim, boxes, scores, labels, counts, keys, pitch);
     return lvq_launch_status();
 }
 

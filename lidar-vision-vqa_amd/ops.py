@@ -790,3 +790,66 @@ def center_collect(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tens
                                         F.ptr(out_b), F.ptr(out_s), F.ptr(out_l), F.ptr(out_n), F.stream_ptr(dev))
     F.check(rc, "lvq_center_collect")
     return out_b, out_s, out_l, out_n
+
+
+HEAD_TASK_C = 16               # output channels per task in the head buffer of sparse_head / voxel_decode
+
+
+def sparse_head(feat: torch.Tensor, nbr: Optional[torch.Tensor], *, k_vol: int, task_n_br, chan_owner, num_conv: int, br_stride: int,
+                w_hi: Optional[torch.Tensor], w_lo: Optional[torch.Tensor], scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
+                w_last: torch.Tensor, bias: torch.Tensor, tag: Optional[str] = None) -> torch.Tensor:
+    """lvq_sparse_head.  feat [N, 128] fp32; nbr [N, k_vol] int32 or None (k_vol 1: row i reads row i); task_n_br and chan_owner
+    ([n_tasks][<= 16] owning branch, negative = nobody) are host lists; w_hi / w_lo [n_tasks, br_stride, k_vol, 128, 128] packed bf16
+    (w_lo None: plain bf16), scale / shift [n_tasks, br_stride, 128], w_last [n_tasks, 16, 128], bias [n_tasks, 16] fp32.
+    Returns the head buffer, CHANNEL-major [16 * n_tasks, N] fp32; channels nobody owns are zeros."""
+    F.require_cuda(feat, nbr, w_hi, w_lo, scale, shift, w_last, bias)
+    if feat.dim() != 2 or feat.dtype != torch.float32:
+        raise F.LvqError(f"sparse_head: expected fp32 [N, C] features, got {feat.dtype} {tuple(feat.shape)}")
+    n, c_in = feat.shape
+    n_tasks, dev = len(task_n_br), feat.device
+    task_c = max(len(r) for r in chan_owner) if len(chan_owner) else 0
+    if len(chan_owner) != n_tasks or any(len(r) != task_c for r in chan_owner):
+        raise F.LvqError("sparse_head: chan_owner is [n_tasks][task_c]")
+    if nbr is not None and (nbr.dtype != torch.int32 or tuple(nbr.shape) != (n, k_vol)):
+        raise F.LvqError(f"sparse_head: nbr is int32 [N, k_vol], got {nbr.dtype} {tuple(nbr.shape)}")
+    out = torch.empty((HEAD_TASK_C * n_tasks, n), dtype=torch.float32, device=dev)
+    with region(tag, dev):
+        rc = F.lib().lvq_sparse_head(F.ptr(feat), n, c_in, F.ptr(nbr), int(k_vol), n_tasks, F.i32x(task_n_br), int(br_stride),
+                                     F.i32x([c for row in chan_owner for c in row]), task_c, int(num_conv), F.ptr(w_hi), F.ptr(w_lo),
+                                     F.ptr(scale), F.ptr(shift), F.ptr(w_last), F.ptr(bias), F.ptr(out), F.stream_ptr(dev))
+    F.check(rc, f"lvq_sparse_head (N={n}, C={c_in}, k_vol={k_vol}, {n_tasks} tasks, num_conv={num_conv})")
+    return out
+
+
+def voxel_decode(head: torch.Tensor, indices: torch.Tensor, batch: int, task_channels, task_n_cls, class_map, *, k: int, box_dim: int,
+                 stride: int, voxel_xy, range_xy, limit_range, score_thresh: Optional[float], tag: Optional[str] = None):
+    """lvq_voxel_decode.  head [c_total, N] fp32 (sparse_head's buffer), indices [N, 3] int32 (b, y, x); the host tables and the geometry
+    are center_decode's.  Returns (boxes [B, T, k, box_dim], scores [B, T, k], labels [B, T, k] int32, counts [B, T] int32): per (scene,
+    task) the min(k, n_cls * n_b) best rows of the scene in descending score order, equal scores towards the lower (class, stored row),
+    rows behind a count zero."""
+    F.require_cuda(head, indices)
+    if head.dim() != 2 or head.dtype != torch.float32 or indices.dtype != torch.int32 or tuple(indices.shape) != (head.shape[1], 3):
+        raise F.LvqError(f"voxel_decode: expected fp32 [C, N] head and int32 [N, 3] indices, got {head.dtype} {tuple(head.shape)} and "
+                         f"{indices.dtype} {tuple(indices.shape)}")
+    c_total, n = head.shape
+    n_tasks, dev, b = len(task_n_cls), head.device, int(batch)
+    if len(task_channels) != n_tasks or any(len(r) != 6 for r in task_channels) or len(class_map) != sum(int(c) for c in task_n_cls):
+        raise F.LvqError("voxel_decode: task_channels is [n_tasks][6], class_map holds sum(task_n_cls) entries")
+    if b <= 0 or k <= 0:
+        raise F.LvqError(f"voxel_decode: batch = {b}, k = {k}")
+    L = F.lib()
+    boxes = torch.empty((b, n_tasks, k, box_dim), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n_tasks, k), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n_tasks, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((b, n_tasks), dtype=torch.int32, device=dev)
+    chans = F.i32x([c for row in task_channels for c in row])
+    args = (F.ptr(head), F.ptr(indices), n, b, c_total, n_tasks, chans, F.i32x(task_n_cls), F.i32x(class_map), k, box_dim, stride,
+            F.f32x(voxel_xy), F.f32x(range_xy), F.f32x(limit_range), -1.0 if score_thresh is None else float(score_thresh), F.ptr(boxes),
+            F.ptr(scores), F.ptr(labels), F.ptr(counts))
+    nb = ctypes.c_size_t(0)
+    rc = L.lvq_voxel_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), n, ctypes.byref(nb))
+    ws = F.workspace(nb.value, dev, "center_head") if rc == F.LVQ_OK else None       # a refused query: the call below names the reason
+    with region(tag, dev):
+        rc = L.lvq_voxel_decode(*args, F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+    F.check(rc, f"lvq_voxel_decode (B={b}, {n_tasks} tasks, {n} rows, K={k})")
+    return boxes, scores, labels, counts

@@ -1,7 +1,9 @@
 """tools/ref_standins.py -- stand-ins for the two libraries the reference's sparse backbones and dynamic VFEs import and this project
 does not have: the small surface of `spconv.pytorch` that pcdet/models/backbones_3d/spconv_backbone*.py touch, and `torch_scatter`'s
 `scatter_mean` / `scatter_max`.  Written from spconv's and torch_scatter's documented behaviour; used ONLY by
-tools/make_lidar_encoder_goldens.py, which runs the reference's unmodified classes on them and stores what they return.  Never
+tools/make_lidar_encoder_goldens.py and tools/make_voxelnext_head_golden.py (the sparse SeparateHead of VoxelNeXtHead: SubMConv2d,
+SparseSequential), which run the reference's unmodified classes on them and store what they return.  A layer's initialisation draws
+from the RNG as spconv 2.x's reset_parameters does (weight, then bias), so the generator state behind a constructor is spconv's.  Never
 imported by the package, by tests/ or by a conftest.
 
 What the stand-in pins, and what it does not.  The fixtures made through it pin the reference's WIRING: which layers a class builds, in
@@ -102,6 +104,9 @@ class SparseConvolution(SparseModule):
         self.weight = nn.Parameter(torch.empty(out_channels, *self.kernel_size, in_channels))
         self.bias = nn.Parameter(torch.zeros(out_channels)) if bias else None
         nn.init.kaiming_uniform_(self.weight, a=math.sqrt(5))
+        if bias:                                  # spconv 2.x's reset_parameters: U(-1 / sqrt(fan_in), 1 / sqrt(fan_in)), drawn after the weight
+            bound = 1.0 / math.sqrt(in_channels * math.prod(self.kernel_size))
+            nn.init.uniform_(self.bias, -bound, bound)
 
     def forward(self, x):
         nd = self.ndim
