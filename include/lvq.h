@@ -69,7 +69,8 @@ typedef struct lvq_tuning {
     int32_t ca_fused_variant;        /* diagnostics builds (CA_DEBUG_VARIANTS) only: timing-ablation variant of k_ca_fused; results are wrong */
     uint64_t ca_fused_stamps;        /* diagnostics: device pointer to [workgroups][4][8] uint64 that k_ca_fused fills with s_memrealtime stamps, or 0 */
     int32_t conv_rows_grid;          /* test hook: workgroups of k_conv_rows (two-launch lvq_bev_tile_kv): 0 built-in grid, n > 0 at most n */
-    int32_t reserved[7];
+    int32_t pillar_vfe_path;         /* single-layer PillarVFE kernel: 0 packed (live points of several pillars per MFMA tile), 1 one pillar per wave; same bits */
+    int32_t reserved[6];
 } lvq_tuning;
 void lvq_tuning_defaults(lvq_tuning *t);
 int lvq_set_tuning(const lvq_tuning *t);      /* NULL restores the defaults */
@@ -138,7 +139,11 @@ int lvq_mean_vfe(const float *voxels, const int32_t *num_pts, int64_t m_cap, con
  *   cout_l > 256 or cin_l > 512, or T * cmax > 20480 with cmax = max(c, every cin_l, 2 cout_l of the non-final layers,
  *   cout of the last): one wave keeps two [T][cmax] fp32 planes in LDS, and the workgroup shrinks from 4 waves to 2 to 1
  *   until they fit in 160 KB.  So every T <= 40 runs at any width the other limits allow, T = 64 up to cmax = 320
- *   (e.g. [64, 64] and [160, 256]), and T = 32 with cout = 256.  Nothing is written when a call is refused. */
+ *   (e.g. [64, 64] and [160, 256]), and T = 32 with cout = 256.  Nothing is written when a call is refused.
+ *   Kernels.  One layer, c = 4, T <= 32, cin <= 12, cout <= 64 and voxels on a 16-byte boundary take the single-layer path:
+ *   by default the packed kernel (two pillars per wave pass, the live points of several pillars per f32 MFMA tile), with
+ *   lvq_tuning.pillar_vfe_path = 1 the one-pillar-per-wave kernel; the two return the same bits.  Everything else, and every
+ *   call under lvq_tuning.pillar_vfe_generic = 1, takes the generic multi-layer kernel (sequential mean: same bound, other bits). */
 int lvq_pillar_vfe(const float *voxels, const int32_t *num_pts, const int32_t *coords_bzyx, int64_t m_cap,
                    const int32_t *n_voxels_dev, int t, int c, int n_layers, const float *const *w_host,
                    const float *const *scale_host, const float *const *shift_host, const int32_t *cin_host,

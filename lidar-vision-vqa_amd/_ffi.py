@@ -33,7 +33,8 @@ class Tuning(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "attn_no32", "attn32_nw", "attn_pipe", "attn_nsplit", "attn_qt", "attn_nw", "gemm_no_gemv", "gemm_stream_c_mb", "gemm_no256",
         "gemm_no256x256", "gemm_256x256_min_tiles", "gemm_ln_tiles", "pillar_vfe_generic", "voxel_path", "pairs_one_wg",
-        "ca_fused_variant")] + [("ca_fused_stamps", ctypes.c_uint64), ("conv_rows_grid", ctypes.c_int32), ("reserved", ctypes.c_int32 * 7)]
+        "ca_fused_variant")] + [("ca_fused_stamps", ctypes.c_uint64), ("conv_rows_grid", ctypes.c_int32), ("pillar_vfe_path", ctypes.c_int32),
+                                   ("reserved", ctypes.c_int32 * 6)]
 
 
 TUNING_FIELDS = tuple(n for n, _ in Tuning._fields_ if n != "reserved")
@@ -62,6 +63,7 @@ def tuning_from_env(env=None) -> dict:
         "voxel_path": 2 if e.get("LVQ_VOXEL_LEGACY") else flag("LVQ_VOXEL_BINNED"),
         "pairs_one_wg": flag("LVQ_PAIRS_ONE_WG"), "ca_fused_variant": num("LVQ_CA_DBG"), "ca_fused_stamps": 0,
         "conv_rows_grid": 0,                   # test hook only: no environment variable
+        "pillar_vfe_path": flag("LVQ_PILLAR_VFE_ONE_PER_WAVE"),
     }
 
 

@@ -252,6 +252,203 @@ __global__ void __launch_bounds__(256) k_pillar_vfe1(const float4 *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------------------------
+// PillarVFE packed path (the default single-layer kernel; k_pillar_vfe1 above stays as the comparator, lvq_tuning.pillar_vfe_path = 1).
+// A LiDAR pillar holds one or two live points against T = 20 or 32 slots, so k_pillar_vfe1's wave per pillar spends its ~160 vector
+// instructions on ~15 useful FMAs per lane.  Here a wave owns PK_PPW consecutive pillars and
+//   * runs the prologue for TWO pillars per pass, one per 32-lane half: the same float4 load, 5-step XOR butterfly (its offsets stay
+//     inside a half; pk_butterfly32 below), divisions and feature expressions as k_pillar_vfe1, operation for operation; the count,
+//     coordinates and points of pass p + 2 are requested before pass p is consumed (two passes in flight);
+//   * stages only the LIVE slots' feature rows (j < min(np, T); ballot + prefix gives the row index) back to back into a ring of five
+//     16-row LDS tiles, each row with its pillar's slot number, and runs every full tile -- rows of several pillars -- as
+//     3 K-steps x 4 column tiles of v_mfma_f32_16x16x4_f32 (four independent chains; a column tile beyond cout multiplies zero weights
+//     and is dropped) from C = 0 with k ascending: bit for bit the fmaf chain of k_pillar_vfe1
+//     (its chain runs over 10 or 12 padded positions, this one always over 12; a padded position is fma(0, 0, acc), which changes nothing
+//     but an accumulator of -0, and after acc * sc + sh and max(., +0) no output bit depends on that sign);
+//   * applies acc * sc + sh (mul, then add), ReLU, and takes the maximum over the pillar's points as an LDS signed-int max on the bit
+//     patterns (values >= +0: see the file header); the slot starts at the pattern of -0, which is below every one of them;
+//   * writes each pillar's row once, lane = channel, after taking the padded-slot value max(0 * sc + sh, 0) exactly when np < T.
+// ---------------------------------------------------------------------------------------------
+constexpr int PK_PPW = 16;        // pillars per wave (8 passes of two)
+constexpr int PK_TILES = 5;       // ring of 16-row tiles: at most 15 rows wait for their tile to fill when a pass adds up to 64
+constexpr int PK_FP = 12;         // padded feature count = 3 K-steps of 4
+constexpr int PK_OSTR = 80;       // row stride of the per-wave output slots (64 channels + 16: neighbouring pillars on different banks)
+
+// The 5-step XOR butterfly over 32 lanes, s[i] += s[i ^ o] for o = 1, 2, 4, 8, 16, without LDS permutes for the first four steps.
+// After steps 1 and 2 the four lanes of a quad hold the same bits (fp32 addition commutes), after step 4 the eight lanes of a half row
+// do: so the partner of step 4 may be ANY lane of the other quad of the half row (row_half_mirror: i -> 7 - i) and the partner of step 8
+// any lane of the other half of the 16-lane row (row_mirror: i -> 15 - i) -- the same operands in the same association as
+// __shfl_xor(s, 4) and __shfl_xor(s, 8).  Step 16 crosses rows: one ds_swizzle (bit mode, xor 0x10 inside each group of 32).
+// Every lane of the wave must be active.
+template <int CTRL>
+__device__ __forceinline__ float pk_add_dpp(float s) {
+    return s + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(s), CTRL, 0xf, 0xf, false));
+}
+__device__ __forceinline__ float pk_butterfly32(float s) {
+    s = pk_add_dpp<0xB1>(s);                                 // quad_perm [1, 0, 3, 2]
+    s = pk_add_dpp<0x4E>(s);                                 // quad_perm [2, 3, 0, 1]
+    s = pk_add_dpp<0x141>(s);                                // row_half_mirror
+    s = pk_add_dpp<0x140>(s);                                // row_mirror
+    return s + __int_as_float(__builtin_amdgcn_ds_swizzle(__float_as_int(s), 0x401F));   // and 0x1f, or 0, xor 0x10
+}
+
+struct PkWave {
+    float feat[PK_TILES * 16][PK_FP];   // [row][k]: row stride 12 words, so the A-operand read (16 rows x 4 k) touches 64 different banks
+    int slot[PK_TILES * 16];            // the row's pillar within the wave's group
+    int omax[(PK_PPW + 1) * PK_OSTR];   // running maximum per (pillar, channel), bit patterns; the last row takes what does not count
+};
+
+// x where keep is all ones, +0 where it is zero
+__device__ __forceinline__ float pk_keep(float x, int keep) { return __int_as_float(__float_as_int(x) & keep); }
+
+template <int FLAGS>   // P.flags (bit0 USE_ABSLOTE_XYZ, bit1 WITH_DISTANCE): the feature row's layout is static, and only bit1 pays for a square root
+__global__ void __launch_bounds__(256) k_pillar_vfe_packed(const float4 *__restrict__ voxels, const int32_t *__restrict__ num_pts,
+                                                           const int32_t *__restrict__ coords, int64_t m_cap,
+                                                           const int32_t *__restrict__ n_live, int T, PfnParams P,
+                                                           float *__restrict__ out) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    __shared__ __attribute__((aligned(16))) PkWave lds[4];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    int64_t m = n_live ? (int64_t)*n_live : m_cap;
+    if (m > m_cap) m = m_cap;
+    const int64_t v_first = ((int64_t)blockIdx.x * 4 + wid) * PK_PPW;
+    if (v_first >= m) return;                                // whole wave exits together; no block barrier below
+    PkWave &L = lds[wid];
+    const int cin = P.cin[0], cout = P.cout[0];
+    constexpr bool abs_xyz = FLAGS & 1;
+    const int half = lane >> 5, j = lane & 31;               // prologue: pillar of the pass, slot
+    const int col = lane & 15, grp = lane >> 4;              // MFMA: column (channel within the tile) / k within the step, row group
+
+    // a pass's inputs, as they lie in memory.  The loads are unconditional at clamped (in-range) addresses; what lies behind the live count
+    // or behind slot T - 1 is masked to zero where the pass is consumed.  (Loads under a lane mask, or a selection right behind them, make
+    // the compiler drain ALL outstanding loads before the current pass's registers are read, which undoes the prefetch.)
+    auto fetch = [&](int pass, int &np_, int4 &co_, float4 &pt_) __attribute__((always_inline)) {
+        if (pass > PK_PPW / 2 - 1) pass = PK_PPW / 2 - 1;    // behind the last pass: its own rows again (cached), never the next group's
+        const int64_t v = v_first + 2 * pass + half;
+        const int64_t vc = v < m ? v : m - 1;                // (m >= 1: v_first < m)
+        np_ = num_pts[vc];
+        co_ = reinterpret_cast<const int4 *>(coords)[vc];        // (b, z, y, x)
+        pt_ = voxels[vc * T + (j < T ? j : T - 1)];
+    };
+    int np_a, np_b; int4 co_a, co_b; float4 pt_a, pt_b;     // two passes in flight: even passes in stage a, odd ones in stage b
+    fetch(0, np_a, co_a, pt_a);
+    fetch(1, np_b, co_b, pt_b);
+
+    // B fragments: w[channel ct * 16 + col][k = 4 ks + grp], zero beyond cin / cout; scale and shift in the accumulator's column map
+    float bw[4][3], scm[4], shm[4];
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) {
+        const int ch = ct * 16 + col;
+        const bool on = ch < cout;
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) {
+            const int k = 4 * ks + grp;
+            bw[ct][ks] = (on && k < cin) ? P.w[0][(size_t)ch * cin + k] : 0.f;
+        }
+        scm[ct] = on ? P.scale[0][ch] : 0.f;
+        shm[ct] = on ? P.shift[0][ch] : 0.f;
+    }
+    // write-out: lane = channel
+    const bool act = lane < cout;
+    const float sc = act ? P.scale[0][lane] : 0.f, sh = act ? P.shift[0][lane] : 0.f;
+    int np_mine = 0;                                         // lane p keeps pillar p's count for the write-out
+    if (lane < PK_PPW && v_first + lane < m) np_mine = num_pts[v_first + lane];
+    for (int e = lane; e < (PK_PPW + 1) * PK_OSTR; e += 64) L.omax[e] = (int)0x80000000;   // -0: below every post-ReLU pattern
+    wave_sync();
+
+    int rows = 0, tiles = 0;                                 // rows staged / tiles consumed so far (wave-uniform)
+    // one 16-row tile through the MFMAs; `rows` bounds the rows that count (the last tile may be part full: an MFMA row depends on its own A row only)
+    auto run_tile = [&](int t) __attribute__((always_inline)) {
+        const int base = (t % PK_TILES) * 16;
+        float a[3];
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) a[ks] = L.feat[base + col][4 * ks + grp];
+        const int4 s4 = *reinterpret_cast<const int4 *>(&L.slot[base + 4 * grp]);
+        const int sl[4] = {s4.x, s4.y, s4.z, s4.w};
+        const int g0 = t * 16 + 4 * grp;
+        // four independent accumulation chains (the column tiles), k ascending in each; column tiles beyond cout multiply zero weights
+        f32x4 acc[4];
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks)
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks], bw[ct][ks], acc[ct], 0, 0, 0);
+        int so[4];                                           // rows behind `rows` (part-full tile) go to the dump slot
+#pragma unroll
+        for (int r = 0; r < 4; ++r) so[r] = (g0 + r < rows ? sl[r] : PK_PPW) * PK_OSTR + col;
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) {
+            if (ct * 16 < cout) {                            // (wave-uniform)
+                const bool on = ct * 16 + col < cout;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float y = fmaxf(acc[ct][r] * scm[ct] + shm[ct], 0.f);     // (mul, then add: -ffp-contract=off)
+                    atomicMax(&L.omax[(on ? so[r] : PK_PPW * PK_OSTR + col) + ct * 16], __float_as_int(y));
+                }
+            }
+        }
+    };
+
+    auto do_pass = [&](int pass, int &np_n, int4 &co_n, float4 &pt_n) __attribute__((always_inline)) {
+        const int on = -(int)(v_first + 2 * pass + half < m);                // all ones / zero
+        const int slot_on = on & -(int)(j < T);
+        const int np = np_n & on; const int4 co = co_n;
+        const float4 pt = make_float4(pk_keep(pt_n.x, slot_on), pk_keep(pt_n.y, slot_on), pk_keep(pt_n.z, slot_on), pk_keep(pt_n.w, slot_on));
+        fetch(pass + 2, np_n, co_n, pt_n);                   // the stage's next pass, requested before this one is consumed
+        // mean over ALL T slots / num_points (pillar_vfe.py:97: padding is zero, no clamp); lanes >= T of each half hold zero
+        const float sx = pk_butterfly32(pt.x), sy = pk_butterfly32(pt.y), sz = pk_butterfly32(pt.z);
+        const float inv_np = (float)np;
+        const float mx_ = sx / inv_np, my_ = sy / inv_np, mz_ = sz / inv_np;
+        float f[PK_FP];
+#pragma unroll
+        for (int k = 0; k < PK_FP; ++k) f[k] = 0.f;
+        const float cl[3] = {pt.x - mx_, pt.y - my_, pt.z - mz_};
+        const float ce[3] = {pt.x - ((float)co.w * P.vs[0] + P.off[0]), pt.y - ((float)co.z * P.vs[1] + P.off[1]),
+                             pt.z - ((float)co.y * P.vs[2] + P.off[2])};
+        if constexpr (abs_xyz) { f[0] = pt.x; f[1] = pt.y; f[2] = pt.z; f[3] = pt.w;
+                                 f[4] = cl[0]; f[5] = cl[1]; f[6] = cl[2]; f[7] = ce[0]; f[8] = ce[1]; f[9] = ce[2]; }
+        else                   { f[0] = pt.w;
+                                 f[1] = cl[0]; f[2] = cl[1]; f[3] = cl[2]; f[4] = ce[0]; f[5] = ce[1]; f[6] = ce[2]; }
+        if constexpr (FLAGS & 2) f[abs_xyz ? 10 : 7] = sqrtf(pt.x * pt.x + pt.y * pt.y + pt.z * pt.z);
+        const bool live = j < np && j < T;                   // padding mask (pillar_vfe.py:117-120): only live slots are staged
+        const unsigned long long mask = __ballot(live);
+        const int g = rows + __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0));
+        if (live) {
+            const int r = ((g >> 4) % PK_TILES) * 16 + (g & 15);
+            float4 *dst = reinterpret_cast<float4 *>(&L.feat[r][0]);
+            dst[0] = make_float4(f[0], f[1], f[2], f[3]);
+            dst[1] = make_float4(f[4], f[5], f[6], f[7]);
+            dst[2] = make_float4(f[8], f[9], f[10], f[11]);
+            L.slot[r] = 2 * pass + half;
+        }
+        rows += __popcll(mask);
+        wave_sync();
+        const int need = pass == PK_PPW / 2 - 1 ? 1 : 16;    // full tiles; after the last pass the part-full one too
+        while (tiles * 16 + need <= rows) { run_tile(tiles); ++tiles; }
+        wave_sync();                                         // the next pass's rows may land in a tile just read
+    };
+    // unrolled: across a loop's back edge the compiler copies the loaded registers into the loop-carried ones, and waits for every load to do so
+#pragma unroll
+    for (int pass = 0; pass < PK_PPW / 2; pass += 2) {
+        do_pass(pass, np_a, co_a, pt_a);
+        do_pass(pass + 1, np_b, co_b, pt_b);
+    }
+    // one 256-byte row per pillar; the padding slots (np .. T - 1) carry all-zero feature rows, so each yields y = (+0) * scale + shift:
+    // taken once, with the same two operations as k_pillar_vfe1, and only where there is a padding slot
+    const float zero = 0.f;
+    const float ypad = fmaxf(zero * sc + sh, 0.f);
+#pragma unroll 4
+    for (int p = 0; p < PK_PPW; ++p) {
+        const int64_t v = v_first + p;
+        if (v >= m) break;                                   // (wave-uniform)
+        const int npv = __builtin_amdgcn_readlane(np_mine, p);
+        float mx = __int_as_float(L.omax[p * PK_OSTR + lane]);
+        if (npv < T) mx = fmaxf(mx, ypad);
+        if (act) out[v * cout + lane] = mx;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // scatter_mean
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_scatter_add(const float *__restrict__ pts, int64_t n, int c, int col0, int nc,
@@ -464,7 +661,19 @@ extern "C" int lvq_pillar_vfe(const float *voxels, const int32_t *num_pts, const
     dim3 grid((unsigned)lvq_cdiv(m_cap, wpb)), block(64 * wpb);
     if (n_layers == 1 && c == 4 && t <= 32 && P.cin[0] <= 12 && P.cout[0] <= 64 && !(((uintptr_t)voxels) & 15) &&
         !lvq_tune().pillar_vfe_generic) {
-        // 4 waves x 8 pillars per workgroup
+        if (lvq_tune().pillar_vfe_path != 1) {
+            // 4 waves x PK_PPW pillars per workgroup
+            const dim3 pgrid((unsigned)lvq_cdiv(m_cap, 4 * PK_PPW));
+            const float4 *v4 = reinterpret_cast<const float4 *>(voxels);
+            switch (flags & 3) {
+            case 0: hipLaunchKernelGGL(k_pillar_vfe_packed<0>, pgrid, block, 0, lvq_s(stream), v4, num_pts, coords_bzyx, m_cap, n_voxels_dev, t, P, out); break;
+            case 1: hipLaunchKernelGGL(k_pillar_vfe_packed<1>, pgrid, block, 0, lvq_s(stream), v4, num_pts, coords_bzyx, m_cap, n_voxels_dev, t, P, out); break;
+            case 2: hipLaunchKernelGGL(k_pillar_vfe_packed<2>, pgrid, block, 0, lvq_s(stream), v4, num_pts, coords_bzyx, m_cap, n_voxels_dev, t, P, out); break;
+            default: hipLaunchKernelGGL(k_pillar_vfe_packed<3>, pgrid, block, 0, lvq_s(stream), v4, num_pts, coords_bzyx, m_cap, n_voxels_dev, t, P, out); break;
+            }
+            return lvq_launch_status();
+        }
+        // the comparator: 4 waves x 8 pillars per workgroup
         hipLaunchKernelGGL(k_pillar_vfe1, dim3((unsigned)lvq_cdiv(m_cap, 32)), block, 0, lvq_s(stream), reinterpret_cast<const float4 *>(voxels), num_pts, coords_bzyx,
                            m_cap, n_voxels_dev, t, P, out);
         return lvq_launch_status();
