@@ -801,6 +801,59 @@ int lvq_voxel_decode(const float *head, const int32_t *indices, int64_t n_rows, 
                      int32_t *labels, int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
 /* =====================================================================================
+ * AnchorHeadSingle (csrc/anchor_head.hip): head maps -> a box for every anchor -> the NMS_PRE_MAXSIZE best -> rotated BEV NMS of up to 4096 rows
+ * ===================================================================================== */
+
+/* generate_predicted_boxes of anchor_head_template.py:225-272 for EVERY anchor of every scene in ONE launch.
+ *   maps          [batch, c_total, h, w] fp32: the raw outputs of conv_cls, conv_box and conv_dir_cls side by side in the channels.
+ *                 cls_channel / box_channel / dir_channel: the first channel of each (dir_channel -1 = no direction classifier); anchor a
+ *                 of a pixel reads channels cls_channel + a * n_cls + k, box_channel + a * 7 + d and dir_channel + a * n_dir_bins + j.
+ *   anchors       [h * w * n_anchors, 7] fp32 on the DEVICE in the reference's flat order (y, x, a): (xa, ya, za, dxa, dya, dza, ra)
+ *   per anchor n = (y * w + x) * n_anchors + a, each step rounded to fp32 in this order (ResidualCoder.decode_torch, box_coder_utils.py:45-80):
+ *                 diag = sqrt(dxa^2 + dya^2); x = xt * diag + xa, y alike; z = zt * dza + za; d* = exp(d*t) * d*a; r = rt + ra.  With a
+ *                 direction classifier: bin = argmax over the bins (ties to the lower bin), v = r - dir_offset, period = 2 pi /
+ *                 n_dir_bins rounded to fp32, r = v - floor(v / period + dir_limit_offset) * period + dir_offset + period * bin.
+ *                 score = max_k sigmoid(logit_k), label = the lowest k that attains it; a NaN logit gives a NaN score.
+ *   outputs       cls_preds [batch, N, n_cls] (the raw logits, regrouped), box_preds [batch, N, 7], scores [batch, N], labels [batch, N]
+ *                 int32 (0-based), N = h * w * n_anchors.
+ *   cand / cand_count   both NULL, or cand [batch, N] int32 and cand_count [batch] int32 (zeroed by the call): the anchors with score >=
+ *                 score_thresh (inclusive, model_nms_utils.py:9; a NaN fails it) as a SET: cand[b, 0 .. cand_count[b] - 1] hold their
+ *                 indices n in NO PARTICULAR ORDER, which may differ from run to run.  lvq_anchor_select does not depend on it.
+ * n_cls <= 64, N < 2^31, batch <= 65535, n_anchors * (n_cls + 10) <= 12284 (a pixel's anchors fit 48 KB of LDS) (else LVQ_EUNSUPPORTED);
+ * NULL operands, non-positive sizes, a channel range outside c_total, one of cand / cand_count without the other: LVQ_EINVAL.  Every
+ * refusal happens before the launch.  No workspace, no allocation, stream-ordered. */
+int lvq_anchor_decode(const float *maps, int batch, int c_total, int h, int w, int cls_channel, int box_channel, int dir_channel,
+                      int n_anchors, int n_cls, int n_dir_bins, float dir_offset, float dir_limit_offset, const float *anchors,
+                      float score_thresh, float *cls_preds, float *box_preds, float *scores, int32_t *labels, int32_t *cand,
+                      int32_t *cand_count, lvq_stream_t stream);
+
+/* class_agnostic_nms of model_nms_utils.py:6-25 up to the NMS call, for every scene in ONE launch (one workgroup per scene).
+ *   scores [batch, n], labels [batch, n] int32, box_preds [batch, n, 7]: lvq_anchor_decode's outputs (or the same made elsewhere)
+ *   candidates    has_thresh != 0: the anchors with score >= score_thresh (a NaN fails it); has_thresh == 0 (SCORE_THRESH None): all
+ *                 anchors, and a NaN of either sign sorts first, as torch.topk has it.
+ *   per scene     the min(pre_max, candidates) largest scores, descending, EQUAL SCORES TOWARDS THE LOWER ANCHOR INDEX:
+ *                 sel_boxes [batch, pre_max, 7], sel_scores [batch, pre_max], sel_labels [batch, pre_max] int32 (as given, 0-based),
+ *                 sel_index [batch, pre_max] int32 (the anchor index), sel_count [batch] int32; rows behind a count are zeros with
+ *                 index -1.  lvq_nms_bev_wide and lvq_center_collect (n_tasks 1, k = pre_max) take them unchanged.
+ *   cand / cand_count   both NULL: the kernel scans all n scores.  Otherwise lvq_anchor_decode's candidate set for the SAME score_thresh
+ *                 (has_thresh must be set): only the list is read; an entry outside 0 .. n - 1 or below the threshold takes no part.
+ *                 The two routes return identical outputs, whatever the order of the list.
+ * pre_max <= 4096 (the sort's 32 KB of LDS), n < 2^31, batch <= 65535 (else LVQ_EUNSUPPORTED); NULL operands, non-positive sizes, a list
+ * without has_thresh: LVQ_EINVAL; ws below the query: LVQ_EWORKSPACE; all before the launch.  The query writes *bytes and returns a status. */
+int lvq_anchor_select_workspace_bytes(int batch, int64_t n, size_t *bytes);
+int lvq_anchor_select(const float *scores, const int32_t *labels, const float *box_preds, int batch, int64_t n, int has_thresh,
+                      float score_thresh, int pre_max, const int32_t *cand, const int32_t *cand_count, float *sel_boxes, float *sel_scores,
+                      int32_t *sel_labels, int32_t *sel_index, int32_t *sel_count, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* lvq_nms_bev for lists of up to 4096 rows (NMS_PRE_MAXSIZE of the anchor heads): the same semantics, outputs, workspace rule and
+ * refusals, with n_max <= 4096.  The same two kernels: up to 64 x 64 mask tiles per group, and a walk that keeps a [64][64] word tile
+ * in LDS (lane w holds word w of the removed set, so 64 words are what one wave walks).  For n_max <= 1024 the keep lists equal
+ * lvq_nms_bev's. */
+int lvq_nms_bev_wide_workspace_bytes(int groups, int n_max, size_t *bytes);
+int lvq_nms_bev_wide(const float *boxes, int box_stride, const int32_t *counts, int groups, int n_max, int pre_max, int post_max, float thresh,
+                     int32_t *keep, int32_t *keep_count, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* =====================================================================================
  * Decode-step runtime
  * ===================================================================================== */
 

@@ -7,6 +7,8 @@ directory, whose on-disk name carries a hyphen).  Sub-packages:
   dense_head  CenterHead (BEV features -> 3-D boxes: conv stack, top-K decode, rotated BEV NMS) with the reference's module API
   sparse_head VoxelNeXtHead (the sparse BEV rows of VoxelResBackBone8xVoxelNeXt -> 3-D boxes: fused branch convs, top-K over rows) and the
               registry of both heads, dense_heads_all
+  anchor_head AnchorHeadSingle (BEV features -> a box for every anchor: one fused 1 x 1 conv, anchor decode) and post_processing (score mask,
+              top 4096, rotated BEV NMS over 64 mask words), the detectors' class-agnostic route; dense_heads_all with all three heads
   fusion  VATBlock / VATLiDAR / VATVision / VisionAdapter with the reference's nn.Module API
   vision_tower  the SAM ViT image encoder (ImageEncoderViT, build_sam_vit_b) with the reference's nn.Module API
   head    prefix assembly + stand-in decoder head

@@ -29,8 +29,11 @@
 // boxes give an area that rounds to zero, identical boxes the full area, and nothing has to be made robust by moving a corner.
 // IoU = area / max(sa + sb - area, 1e-8), as iou3d_nms_kernel.cu:217-234 divides.
 //
+// The selection (key_of, select_sort), the rectangles (Rect, rect_iou) and k_nms_mask / k_nms_walk live in head_common.h, which
+// anchor_head.hip shares; this file instantiates them for 1024 threads, 1024 sort rows and 16 mask words.
+//
 // Every store below is an ordinary vector store from C++; LDS counters use ds atomics.
-#include "common.h"
+#include "head_common.h"
 
 namespace {
 
@@ -49,134 +52,6 @@ struct CenterTasks {                   // by value in the kernel arguments
 struct CenterGeom {
     float stride, vx, vy, rx, ry, lim[6], thresh;
 };
-
-// fp32 bits -> unsigned key with the order of the floats (negative values below positive ones).  Every NaN, whatever its sign bit and
-// payload, gets the one top key: sigmoid(+NaN) carries the sign bit of -NaN through exp, the add and the divide, and would sort last.
-__device__ __forceinline__ uint32_t key_of(float f) {
-    const uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float score_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// LDS of the selection, shared by k_center_decode and k_voxel_decode
-struct SelectLds {
-    uint64_t buf[MAX_K];
-    uint32_t hist[256], scan[2][256];
-    uint32_t sel_bin, sel_above, sel_cnt, ncand;
-    uint32_t wcnt[DEC_THREADS / 64];
-};
-
-// histogram of byte `shift` of the keys that agree with `prefix` above it.  Neighbouring candidates mostly fall into one bin, so a thread
-// counts a run in a register and touches the LDS counter once per run.  key_at(i) is the key of flat index i, or 0 for an index that is
-// no candidate (SPARSE only: key_of never returns 0, the lowest key is -inf's 0x007fffff).
-template <bool FIRST, bool SPARSE, class KeyAt>
-__device__ void radix_hist(KeyAt key_at, uint32_t *keys, int n, uint32_t prefix, int shift, uint32_t *hist) {
-    int run_bin = -1;
-    uint32_t run = 0;
-    const uint32_t hi_mask = shift == 24 ? 0u : ~((1u << (shift + 8)) - 1u);
-    for (int i = threadIdx.x; i < n; i += DEC_THREADS) {
-        uint32_t k;
-        if (FIRST) { k = key_at(i); keys[i] = k; }
-        else k = keys[i];
-        if (SPARSE && k == 0u) continue;
-        if ((k & hi_mask) != prefix) continue;
-        const int bin = (int)((k >> shift) & 255u);
-        if (bin != run_bin) {
-            if (run) atomicAdd(&hist[run_bin], run);
-            run_bin = bin; run = 0;
-        }
-        ++run;
-    }
-    if (run) atomicAdd(&hist[run_bin], run);
-}
-
-// The K largest keys of key_at(0 .. n - 1), K >= 1 and at most the number of candidates, into s.buf[0 .. K - 1] as (key << 32 | ~index),
-// descending: a 4 x 8-bit radix select of the K-th key, equal keys towards the lower flat index, then a bitonic sort.  keys [n] is the
-// group's scratch in global memory.  Every thread of the workgroup calls it.
-template <bool SPARSE, class KeyAt>
-__device__ void select_sort(SelectLds &s, KeyAt key_at, uint32_t *keys, int n, int K) {
-    uint64_t *buf = s.buf;
-    uint32_t *hist = s.hist, *wcnt = s.wcnt;
-    const int tid = threadIdx.x;
-    // ---- the K-th largest key: four passes of 8 bits, most significant first
-    uint32_t prefix = 0, need = (uint32_t)K;
-    for (int pass = 0; pass < 4; ++pass) {
-        const int shift = 24 - 8 * pass;
-        if (tid < 256) hist[tid] = 0;
-        __syncthreads();
-        if (pass == 0) radix_hist<true, SPARSE>(key_at, keys, n, prefix, shift, hist);
-        else radix_hist<false, SPARSE>(key_at, keys, n, prefix, shift, hist);
-        __syncthreads();
-        // suffix sums over the 256 bins (Hillis-Steele, 8 steps)
-        if (tid < 256) s.scan[0][tid] = hist[tid];
-        __syncthreads();
-        int cur = 0;
-        for (int d = 1; d < 256; d <<= 1) {
-            if (tid < 256) s.scan[cur ^ 1][tid] = s.scan[cur][tid] + (tid + d < 256 ? s.scan[cur][tid + d] : 0u);
-            __syncthreads();
-            cur ^= 1;
-        }
-        if (tid < 256) {
-            const uint32_t incl = s.scan[cur][tid], above = incl - hist[tid];
-            if (above < need && incl >= need) { s.sel_bin = (uint32_t)tid; s.sel_above = above; s.sel_cnt = hist[tid]; }
-        }
-        __syncthreads();
-        prefix |= s.sel_bin << shift;
-        need -= s.sel_above;
-        __syncthreads();
-    }
-    const uint32_t T = prefix, eq_cnt = s.sel_cnt;     // `need` of the eq_cnt keys equal to T belong to the K winners
-    if (tid == 0) s.ncand = 0;
-    __syncthreads();
-    const bool all_equal = need == eq_cnt;
-    for (int i = tid; i < n; i += DEC_THREADS) {
-        const uint32_t k = keys[i];
-        if (k > T || (all_equal && k == T)) {
-            const uint32_t slot = atomicAdd(&s.ncand, 1u);
-            if (slot < (uint32_t)MAX_K) buf[slot] = ((uint64_t)k << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
-        }
-    }
-    if (!all_equal) {
-        // more keys equal the K-th than there is room for: the lowest flat indices win.  Each thread owns a contiguous range.
-        const int chunk = (n + DEC_THREADS - 1) / DEC_THREADS, lo = tid * chunk, hi = min(n, lo + chunk);
-        uint32_t mine = 0;
-        for (int i = lo; i < hi; ++i) mine += keys[i] == T;
-        uint32_t before = 0;                                     // exclusive prefix: wave partials, then the waves before this one
-        {
-            const int lane = tid & 63, wave = tid >> 6;
-            uint32_t v = mine;
-            for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(v, d); if (lane >= d) v += o; }
-            if (lane == 63) wcnt[wave] = v;
-            __syncthreads();
-            for (int q = 0; q < wave; ++q) before += wcnt[q];
-            before += v - mine;
-            __syncthreads();
-        }
-        for (int i = lo; i < hi && before < need; ++i)
-            if (keys[i] == T) {
-                const uint32_t slot = atomicAdd(&s.ncand, 1u);
-                if (slot < (uint32_t)MAX_K) buf[slot] = ((uint64_t)T << 32) | (uint64_t)(0xffffffffu - (uint32_t)i);
-                ++before;
-            }
-    }
-    __syncthreads();
-    // ---- sort the K winners: (key, ~index) descending, bitonic over the next power of two
-    int P = 2;
-    while (P < K) P <<= 1;
-    if (tid < P && tid >= K) buf[tid] = 0;
-    __syncthreads();
-    for (int k2 = 2; k2 <= P; k2 <<= 1)
-        for (int j = k2 >> 1; j > 0; j >>= 1) {
-            const int other = tid ^ j;
-            if (tid < P && other > tid) {
-                const uint64_t a = buf[tid], c = buf[other];
-                const bool desc = (tid & k2) == 0;
-                if (desc ? a < c : a > c) { buf[tid] = c; buf[other] = a; }
-            }
-            __syncthreads();
-        }
-}
 
 // the box of a candidate at cell (x, y); ch(c) reads channel c at the candidate (centernet_utils.py:184-212 / 310-319)
 template <class Ch>
@@ -226,13 +101,13 @@ __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__re
                                                                 float *__restrict__ boxes, float *__restrict__ scores,
                                                                 int32_t *__restrict__ labels, int32_t *__restrict__ counts,
                                                                 uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
-    __shared__ SelectLds s;
+    __shared__ SelectLds<DEC_THREADS, MAX_K> s;
     const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
     const int64_t hw = (int64_t)h * w;
     const int n = (int)(tk.n_cls[t] * hw);
     const float *scene = maps + (int64_t)b * c_total * hw;
     const float *hm = scene + (int64_t)tk.off[t][5] * hw;
-    select_sort<false>(s, [hm](int i) { return key_of(1.0f / (1.0f + expf(-hm[i]))); }, keys_ws + (int64_t)g * keys_pitch, n, K);
+    select_sort<DEC_THREADS, MAX_K, false>(s, [hm](int i) { return key_of(1.0f / (1.0f + expf(-hm[i]))); }, keys_ws + (int64_t)g * keys_pitch, n, K);
     // ---- decode, mask, compact (centernet_utils.py:184-221)
     bool keep = false;
     float bx[9];
@@ -258,7 +133,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_voxel_decode(const float *__res
                                                                float *__restrict__ boxes, float *__restrict__ scores,
                                                                int32_t *__restrict__ labels, int32_t *__restrict__ counts,
                                                                uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
-    __shared__ SelectLds s;
+    __shared__ SelectLds<DEC_THREADS, MAX_K> s;
     const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
     const int n_cls = tk.n_cls[t];
     const float *hm = head + (int64_t)tk.off[t][5] * n_rows;
@@ -274,7 +149,7 @@ __global__ __launch_bounds__(DEC_THREADS) void k_voxel_decode(const float *__res
     const int k_eff = (int)(cand < K ? cand : K);
     __syncthreads();
     if (k_eff > 0)                                               // (workgroup-uniform)
-        select_sort<true>(s, [=](int i) {
+        select_sort<DEC_THREADS, MAX_K, true>(s, [=](int i) {
             const int row = i % n_rows;
             return indices[3 * (int64_t)row] == b ? key_of(1.0f / (1.0f + expf(-hm[i]))) : 0u;
         }, keys_ws + (int64_t)g * keys_pitch, n_cls * n_rows, k_eff);
@@ -295,149 +170,11 @@ __global__ __launch_bounds__(DEC_THREADS) void k_voxel_decode(const float *__res
     compact_store(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------------
-// rotated rectangles
-// ---------------------------------------------------------------------------------------------------------------------------------
-struct Rect { float x, y, hx, hy, c, s; };        // centre, half extents, cos / sin of the heading
-
-__device__ __forceinline__ Rect rect_of(const float *p) {
-    Rect r;
-    r.x = p[0]; r.y = p[1]; r.hx = 0.5f * p[3]; r.hy = 0.5f * p[4];
-    sincosf(p[6], &r.s, &r.c);
-    return r;
-}
-
-// one Sutherland-Hodgman step against the half-plane sign * coord <= d, coord = x (AXIS 0) or y (AXIS 1); returns the new vertex count
-template <int AXIS>
-__device__ __forceinline__ int clip_plane(const float *px, const float *py, int n, float sign, float d, float *qx, float *qy) {
-    int m = 0;
-    for (int i = 0; i < n; ++i) {
-        const int j = i + 1 == n ? 0 : i + 1;
-        const float vi = sign * (AXIS == 0 ? px[i] : py[i]) - d, vj = sign * (AXIS == 0 ? px[j] : py[j]) - d;
-        const bool in_i = vi <= 0.f, in_j = vj <= 0.f;
-        if (in_i && m < 8) { qx[m] = px[i]; qy[m] = py[i]; ++m; }
-        if (in_i != in_j && m < 8) {
-            const float tt = vi / (vi - vj);
-            qx[m] = px[i] + tt * (px[j] - px[i]);
-            qy[m] = py[i] + tt * (py[j] - py[i]);
-            ++m;
-        }
-    }
-    return m;
-}
-
-__device__ float rect_iou(const Rect &a, const Rect &b) {
-    const float dx = a.x - b.x, dy = a.y - b.y;
-    const float ra = a.hx + a.hy, rb = b.hx + b.hy;                       // >= the half diagonals
-    if (dx * dx + dy * dy > (ra + rb) * (ra + rb)) return 0.f;            // the circumscribed circles are apart: the area is exactly zero
-    const float ox = dx * b.c + dy * b.s, oy = dy * b.c - dx * b.s;       // a's centre in b's frame
-    const float cr = a.c * b.c + a.s * b.s, sr = a.s * b.c - a.c * b.s;   // a's heading relative to b's
-    const float ux = cr * a.hx, uy = sr * a.hx, vx = -sr * a.hy, vy = cr * a.hy;
-    float px[8], py[8], qx[8], qy[8];
-    px[0] = ox + ux + vx; py[0] = oy + uy + vy;
-    px[1] = ox - ux + vx; py[1] = oy - uy + vy;
-    px[2] = ox - ux - vx; py[2] = oy - uy - vy;
-    px[3] = ox + ux - vx; py[3] = oy + uy - vy;
-    int n = clip_plane<0>(px, py, 4, 1.f, b.hx, qx, qy);
-    n = clip_plane<0>(qx, qy, n, -1.f, b.hx, px, py);
-    n = clip_plane<1>(px, py, n, 1.f, b.hy, qx, qy);
-    n = clip_plane<1>(qx, qy, n, -1.f, b.hy, px, py);
-    float twice = 0.f;
-    for (int i = 0; i < n; ++i) {
-        const int j = i + 1 == n ? 0 : i + 1;
-        twice += px[i] * py[j] - px[j] * py[i];
-    }
-    const float inter = 0.5f * fabsf(twice);
-    const float sa = 4.f * a.hx * a.hy, sb = 4.f * b.hx * b.hy;
-    return inter / fmaxf(sa + sb - inter, 1e-8f);
-}
-
 __global__ __launch_bounds__(256) void k_boxes_iou_bev(const float *__restrict__ a, int n, const float *__restrict__ bb, int m,
                                                         float *__restrict__ iou) {
     const int j = blockIdx.x * 64 + threadIdx.x, i = blockIdx.y * 4 + threadIdx.y;
     if (i >= n || j >= m) return;
     iou[(int64_t)i * m + j] = rect_iou(rect_of(a + (int64_t)i * 7), rect_of(bb + (int64_t)j * 7));
-}
-
-__device__ __forceinline__ int group_count(const int32_t *counts, int g, int n_max, int pre_max) {
-    return max(0, min(min(counts[g], n_max), pre_max));
-}
-
-__global__ __launch_bounds__(64) void k_nms_mask(const float *__restrict__ boxes, int box_stride, const int32_t *__restrict__ counts,
-                                                  int n_max, int pre_max, float thresh, uint64_t *__restrict__ mask, int n_words) {
-    __shared__ Rect rows[64];
-    const int ct = blockIdx.x, rt = blockIdx.y, g = blockIdx.z, lane = threadIdx.x;
-    if (ct < rt) return;                                        // strictly below the diagonal: a box is suppressed by EARLIER rows only
-    const int n = group_count(counts, g, n_max, pre_max);
-    if (ct * 64 >= n) return;                                   // the walk reads words 0 .. ceil(n / 64) - 1 of rows below n only
-    const float *base = boxes + (int64_t)g * n_max * box_stride;
-    const int col = ct * 64 + lane, row_l = rt * 64 + lane;
-    Rect mine = {0.f, 0.f, 0.f, 0.f, 1.f, 0.f};
-    if (col < n) mine = rect_of(base + (int64_t)col * box_stride);
-    if (row_l < n) rows[lane] = rect_of(base + (int64_t)row_l * box_stride);
-    __syncthreads();
-    uint64_t word = 0;
-    const int n_rows = min(64, n - rt * 64);
-    for (int i = 0; i < n_rows; ++i) {
-        const int row = rt * 64 + i;
-        float v = 0.f;
-        if (col < n && col > row) v = rect_iou(rows[i], mine);
-        const uint64_t bal = __ballot(v > thresh);
-        if (lane == i) word = bal;
-    }
-    if (row_l < n) mask[((int64_t)g * n_max + row_l) * n_words + ct] = word;
-}
-
-__global__ __launch_bounds__(64) void k_nms_walk(const uint64_t *__restrict__ mask, const int32_t *__restrict__ counts, int n_max,
-                                                  int pre_max, int post_max, int n_words, int32_t *__restrict__ keep,
-                                                  int32_t *__restrict__ keep_count) {
-    __shared__ uint64_t tile[64][NMS_WORDS];
-    const int g = blockIdx.x, lane = threadIdx.x;
-    const int n = group_count(counts, g, n_max, pre_max);
-    const uint64_t *gm = mask + (int64_t)g * n_max * n_words;
-    int32_t *out = keep + (int64_t)g * post_max;
-    uint64_t remv = 0;                                          // lane w holds word w of the removed set
-    int cnt = 0;
-    const int chunks = (n + 63) / 64;
-    for (int c = 0; c < chunks && cnt < post_max; ++c) {
-        const int rows_here = min(64, n - c * 64);
-        // this chunk's rows, words c .. chunks - 1 (what k_nms_mask wrote), into LDS
-        for (int e = lane; e < 64 * NMS_WORDS; e += 64) {
-            const int r = e / NMS_WORDS, wd = e - r * NMS_WORDS;
-            tile[r][wd] = (r < rows_here && wd >= c && wd < chunks) ? gm[(int64_t)(c * 64 + r) * n_words + wd] : 0ull;
-        }
-        __syncthreads();
-        // the chunk's own decisions need the diagonal word alone: 64 uniform steps
-        const uint64_t diag = tile[lane][c];
-        const uint32_t d_lo = (uint32_t)diag, d_hi = (uint32_t)(diag >> 32);
-        const uint32_t r_lo = (uint32_t)remv, r_hi = (uint32_t)(remv >> 32);
-        uint64_t cur = ((uint64_t)(uint32_t)__shfl((int)r_hi, c) << 32) | (uint32_t)__shfl((int)r_lo, c);
-        if (rows_here < 64) cur |= ~0ull << rows_here;
-        uint64_t kept = 0;
-        for (int j = 0; j < rows_here; ++j) {
-            if ((cur >> j) & 1ull) continue;
-            kept |= 1ull << j;
-            cur |= ((uint64_t)(uint32_t)__shfl((int)d_hi, j) << 32) | (uint32_t)__shfl((int)d_lo, j);
-        }
-        // later words: lane w ORs the kept rows' word w
-        if (lane > c && lane < chunks) {
-            uint64_t k2 = kept;
-            while (k2) {
-                const int j = __ffsll((unsigned long long)k2) - 1;
-                k2 &= k2 - 1;
-                remv |= tile[j][lane];
-            }
-        }
-        if ((kept >> lane) & 1ull) {
-            const int pos = cnt + __popcll(kept & ((1ull << lane) - 1ull));
-            if (pos < post_max) out[pos] = c * 64 + lane;
-        }
-        cnt += __popcll(kept);
-        __syncthreads();
-    }
-    cnt = min(cnt, post_max);
-    for (int e = cnt + lane; e < post_max; e += 64) out[e] = -1;
-    if (lane == 0) keep_count[g] = cnt;
 }
 
 __global__ __launch_bounds__(256) void k_center_collect(const float *__restrict__ boxes, const float *__restrict__ scores,
@@ -467,8 +204,6 @@ __global__ __launch_bounds__(256) void k_center_collect(const float *__restrict_
         out_labels[to] = (int64_t)labels[from] + 1;             // center_head.py:363: labels are 1-based
     }
 }
-
-size_t nms_words(int n_max) { return (size_t)((n_max + 63) / 64); }
 
 }  // namespace
 
@@ -610,16 +345,7 @@ extern "C" int lvq_nms_bev(const float *boxes, int box_stride, const int32_t *co
     const int rc = lvq_nms_bev_workspace_bytes(groups, n_max, &need);
     if (rc != LVQ_OK) return rc;
     if (!ws || ws_bytes < need) return LVQ_EWORKSPACE;
-    LvqArena arena(ws, ws_bytes);
-    const int n_words = (int)nms_words(n_max);
-    uint64_t *mask = arena.take<uint64_t>((size_t)groups * n_max * n_words);
-    if (!arena.ok) return LVQ_EWORKSPACE;
-    hipStream_t st = lvq_s(stream);
-    hipLaunchKernelGGL(k_nms_mask, dim3((unsigned)n_words, (unsigned)n_words, (unsigned)groups), dim3(64), 0, st, boxes, box_stride, counts,
-                       n_max, pre_max, thresh, mask, n_words);
-    hipLaunchKernelGGL(k_nms_walk, dim3((unsigned)groups), dim3(64), 0, st, (const uint64_t *)mask, counts, n_max, pre_max, post_max, n_words,
-                       keep, keep_count);
-    return lvq_launch_status();
+    return nms_launch<NMS_WORDS>(boxes, box_stride, counts, groups, n_max, pre_max, post_max, thresh, keep, keep_count, ws, ws_bytes, stream);
 }
 
 extern "C" int lvq_center_collect(const float *boxes, const float *scores, const int32_t *labels, const int32_t *keep,

@@ -853,3 +853,88 @@ def voxel_decode(head: torch.Tensor, indices: torch.Tensor, batch: int, task_cha
         rc = L.lvq_voxel_decode(*args, F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(dev))
     F.check(rc, f"lvq_voxel_decode (B={b}, {n_tasks} tasks, {n} rows, K={k})")
     return boxes, scores, labels, counts
+
+
+def anchor_decode(maps: torch.Tensor, anchors: torch.Tensor, *, n_anchors: int, n_cls: int, cls_channel: int, box_channel: int,
+                  dir_channel: int = -1, n_dir_bins: int = 0, dir_offset: float = 0.0, dir_limit_offset: float = 0.0,
+                  score_thresh: Optional[float] = None, tag: Optional[str] = None):
+    """lvq_anchor_decode.  maps [B, c_total, H, W] fp32 (cls | box | dir channels from the given first channels; dir_channel -1: no
+    direction classifier), anchors [H * W * n_anchors, 7] fp32 in the flat order (y, x, a).  Returns (cls_preds [B, N, n_cls], box_preds
+    [B, N, 7], scores [B, N], labels [B, N] int32 0-based, cand, cand_count): with a score_thresh, cand [B, N] int32 holds in its first
+    cand_count[b] entries the anchors with score >= score_thresh, in no particular order; without one both are None."""
+    F.require_cuda(maps, anchors)
+    if maps.dim() != 4 or maps.dtype != torch.float32 or not maps.is_contiguous():
+        raise F.LvqError(f"anchor_decode: expected contiguous fp32 [B, C, H, W] maps, got {maps.dtype} {tuple(maps.shape)}")
+    b, c_total, h, w = maps.shape
+    n, dev = h * w * int(n_anchors), maps.device
+    if anchors.dtype != torch.float32 or tuple(anchors.shape) != (n, 7) or not anchors.is_contiguous():
+        raise F.LvqError(f"anchor_decode: expected contiguous fp32 anchors [{n}, 7], got {anchors.dtype} {tuple(anchors.shape)}")
+    cls_preds = torch.empty((b, n, n_cls), dtype=torch.float32, device=dev)
+    box_preds = torch.empty((b, n, 7), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n), dtype=torch.int32, device=dev)
+    cand = cand_count = None
+    if score_thresh is not None:
+        cand = torch.empty((b, n), dtype=torch.int32, device=dev)
+        cand_count = torch.empty((b,), dtype=torch.int32, device=dev)
+    with region(tag, dev):
+        rc = F.lib().lvq_anchor_decode(F.ptr(maps), b, c_total, h, w, int(cls_channel), int(box_channel), int(dir_channel), int(n_anchors),
+                                       int(n_cls), int(n_dir_bins), float(dir_offset), float(dir_limit_offset), F.ptr(anchors),
+                                       0.0 if score_thresh is None else float(score_thresh), F.ptr(cls_preds), F.ptr(box_preds),
+                                       F.ptr(scores), F.ptr(labels), F.ptr(cand), F.ptr(cand_count), F.stream_ptr(dev))
+    F.check(rc, f"lvq_anchor_decode (B={b}, {h} x {w}, {n_anchors} anchors, {n_cls} classes)")
+    return cls_preds, box_preds, scores, labels, cand, cand_count
+
+
+def anchor_select(scores: torch.Tensor, labels: torch.Tensor, box_preds: torch.Tensor, *, score_thresh: Optional[float], pre_max: int,
+                  cand: Optional[torch.Tensor] = None, cand_count: Optional[torch.Tensor] = None, tag: Optional[str] = None):
+    """lvq_anchor_select.  scores [B, N] fp32, labels [B, N] int32, box_preds [B, N, 7] fp32; score_thresh None takes every anchor.
+    Returns (sel_boxes [B, pre_max, 7], sel_scores, sel_labels int32, sel_index int32, sel_count [B] int32): per scene the
+    min(pre_max, candidates) best in descending score order, equal scores towards the lower anchor index; rows behind a count are zeros
+    with index -1.  cand / cand_count: anchor_decode's candidate set for the same threshold (the scan is skipped)."""
+    F.require_cuda(scores, labels, box_preds, cand, cand_count)
+    if scores.dim() != 2 or scores.dtype != torch.float32 or labels.dtype != torch.int32 or labels.shape != scores.shape or \
+            box_preds.dtype != torch.float32 or tuple(box_preds.shape) != (*scores.shape, 7) or \
+            not (scores.is_contiguous() and labels.is_contiguous() and box_preds.is_contiguous()):
+        raise F.LvqError(f"anchor_select: expected contiguous fp32 scores [B, N], int32 labels [B, N] and fp32 boxes [B, N, 7], got "
+                         f"{tuple(scores.shape)}, {tuple(labels.shape)} and {tuple(box_preds.shape)}")
+    b, n = scores.shape
+    if (cand is None) != (cand_count is None) or (cand is not None and (cand.dtype != torch.int32 or tuple(cand.shape) != (b, n) or
+                                                                         cand_count.dtype != torch.int32 or cand_count.numel() != b)):
+        raise F.LvqError("anchor_select: cand is int32 [B, N] and cand_count int32 [B], or both are None")
+    dev, L, pre_max = scores.device, F.lib(), int(pre_max)
+    rows = max(pre_max, 1)
+    sel_boxes = torch.empty((b, rows, 7), dtype=torch.float32, device=dev)
+    sel_scores = torch.empty((b, rows), dtype=torch.float32, device=dev)
+    sel_labels = torch.empty((b, rows), dtype=torch.int32, device=dev)
+    sel_index = torch.empty((b, rows), dtype=torch.int32, device=dev)
+    sel_count = torch.empty((b,), dtype=torch.int32, device=dev)
+    nb = ctypes.c_size_t(0)
+    rc = L.lvq_anchor_select_workspace_bytes(b, n, ctypes.byref(nb))
+    ws = F.workspace(nb.value, dev, "anchor_head") if rc == F.LVQ_OK else None       # a refused query: the call below names the reason
+    with region(tag, dev):
+        rc = L.lvq_anchor_select(F.ptr(scores), F.ptr(labels), F.ptr(box_preds), b, n, int(score_thresh is not None),
+                                 0.0 if score_thresh is None else float(score_thresh), pre_max, F.ptr(cand), F.ptr(cand_count),
+                                 F.ptr(sel_boxes), F.ptr(sel_scores), F.ptr(sel_labels), F.ptr(sel_index), F.ptr(sel_count), F.ptr(ws),
+                                 ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+    F.check(rc, f"lvq_anchor_select (B={b}, N={n}, pre_max={pre_max})")
+    return sel_boxes, sel_scores, sel_labels, sel_index, sel_count
+
+
+def nms_bev_wide(boxes: torch.Tensor, counts: torch.Tensor, *, thresh: float, pre_max: int, post_max: int, tag: Optional[str] = None):
+    """lvq_nms_bev_wide: nms_bev for groups of up to 4096 rows.  boxes [G, N_max, >= 7] fp32, each group in descending score order;
+    counts [G] int32 on the device.  Returns (keep [G, post_max] int32, keep_count [G] int32).  No host read."""
+    F.require_cuda(boxes, counts)
+    if boxes.dim() != 3 or boxes.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != boxes.shape[0]:
+        raise F.LvqError(f"nms_bev_wide: expected fp32 boxes [G, N, >= 7] and int32 counts [G], got {tuple(boxes.shape)} and {tuple(counts.shape)}")
+    g, n_max, stride = boxes.shape
+    dev, L = boxes.device, F.lib()
+    keep = torch.empty((g, post_max), dtype=torch.int32, device=dev)
+    keep_count = torch.empty((g,), dtype=torch.int32, device=dev)
+    ws = F.workspace(_ws_query(L.lvq_nms_bev_wide_workspace_bytes, f"lvq_nms_bev_wide_workspace_bytes ({g} groups of {n_max})", g, n_max), dev,
+                     "anchor_head_nms")
+    with region(tag, dev):
+        rc = L.lvq_nms_bev_wide(F.ptr(boxes), stride, F.ptr(counts), g, n_max, int(pre_max), int(post_max), float(thresh), F.ptr(keep),
+                                F.ptr(keep_count), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
+    F.check(rc, f"lvq_nms_bev_wide ({g} groups of {n_max})")
+    return keep, keep_count
