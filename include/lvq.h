@@ -831,7 +831,8 @@ int lvq_anchor_decode(const float *maps, int batch, int c_total, int h, int w, i
  *   scores [batch, n], labels [batch, n] int32, box_preds [batch, n, 7]: lvq_anchor_decode's outputs (or the same made elsewhere)
  *   candidates    has_thresh != 0: the anchors with score >= score_thresh (a NaN fails it); has_thresh == 0 (SCORE_THRESH None): all
  *                 anchors, and a NaN of either sign sorts first, as torch.topk has it.
- *   per scene     the min(pre_max, candidates) largest scores, descending, EQUAL SCORES TOWARDS THE LOWER ANCHOR INDEX:
+ *   per scene     the min(pre_max, candidates) largest scores, descending, EQUAL SCORES TOWARDS THE LOWER ANCHOR INDEX (-0.0 and +0.0
+ *                 are equal scores: between them the index decides, as `>=` and torch.topk compare them; any sign is accepted):
  *                 sel_boxes [batch, pre_max, 7], sel_scores [batch, pre_max], sel_labels [batch, pre_max] int32 (as given, 0-based),
  *                 sel_index [batch, pre_max] int32 (the anchor index), sel_count [batch] int32; rows behind a count are zeros with
  *                 index -1.  lvq_nms_bev_wide and lvq_center_collect (n_tasks 1, k = pre_max) take them unchanged.

@@ -22,8 +22,12 @@ forward(data_dict), eval() under torch.no_grad():
           (POST_PROCESSING.SCORE_THRESH lives outside the head's own configuration) -- the set of anchors that reach it.
   writes  the reference's contract: data_dict['batch_cls_preds'] [B, N, n_cls] (raw logits), ['batch_box_preds'] [B, N, 7],
           ['cls_preds_normalized'] = False; and ours: ['anchor_scores'], ['anchor_labels'] [B, N] (also in forward_ret_dict) and
-          ['anchor_candidates'] (the threshold, the list, its counts) or None, and ['anchor_source'], the two dense tensors themselves, by
-          which post_processing recognises that scores and labels belong to the batch_cls_preds it was given.
+          ['anchor_candidates'] (the threshold, the list, its counts) or None, and ['anchor_source'], the two dense tensors themselves
+          and the version of batch_cls_preds (_ffi.version_of), by which post_processing recognises that scores and labels belong to
+          the batch_cls_preds it was given: another tensor, or the same one edited in place since, takes the "from elsewhere" route.
+          batch_box_preds is read as it is at the call, so an edit of it needs no such check.  Under torch.inference_mode() the
+          outputs are inference tensors, which count no versions: no version is recorded and post_processing always takes the "from
+          elsewhere" route for them (an in-place edit could not be seen there).
 
 post_processing, MULTI_CLASSES_NMS False, NMS_TYPE nms_gpu:
   ONE lvq_anchor_select (score mask `>=`, top NMS_PRE_MAXSIZE, equal scores towards the lower anchor index), ONE lvq_nms_bev_wide (two
@@ -313,7 +317,7 @@ class AnchorHeadSingle(nn.Module):
         data_dict["cls_preds_normalized"] = False
         data_dict["anchor_scores"], data_dict["anchor_labels"] = scores, labels
         data_dict["anchor_candidates"] = None if cand is None else (float(thresh), cand, cand_count)
-        data_dict["anchor_source"] = (cls_preds, box_preds)
+        data_dict["anchor_source"] = (cls_preds, box_preds, None if cls_preds.is_inference() else F.version_of((cls_preds,)))
         return data_dict
 
 
@@ -350,13 +354,16 @@ def post_processing(batch_dict, post_process_cfg, num_class):
     batch_size = int(batch_dict["batch_size"])
     if batch_size != box.shape[0]:
         raise F.LvqError(f"post_processing: batch_size = {batch_size}, batch_box_preds holds {box.shape[0]} scenes")
-    F.require_cuda(cls, box)
+    for t in (cls, box):                               # a view such as batch_cls_preds[..., :1] is fine: nothing below needs its layout
+        if not t.is_cuda:
+            F.require_cuda(t)
     normalized = bool(batch_dict.get("cls_preds_normalized", False))
     if os.environ.get("LVQ_HEAD_TORCH_POST"):
         return _torch_post(cls, box, normalized, post), {}
     src = batch_dict.get("anchor_source")
     cand = cand_count = None
-    if src is not None and src[0] is cls and src[1] is box and not normalized:
+    if src is not None and src[0] is cls and src[1] is box and not normalized and not cls.is_inference() and \
+            src[2] is not None and F.version_of((cls,)) == src[2]:
         scores, labels = batch_dict["anchor_scores"], batch_dict["anchor_labels"]
         listed = batch_dict.get("anchor_candidates")
         if listed is not None and post["thresh"] is not None and np.float32(listed[0]) == np.float32(post["thresh"]):

@@ -12,9 +12,12 @@ namespace {
 
 // fp32 bits -> unsigned key with the order of the floats (negative values below positive ones).  Every NaN, whatever its sign bit and
 // payload, gets the one top key: sigmoid(+NaN) carries the sign bit of -NaN through exp, the add and the divide, and would sort last.
+// -0.0 gets the key of +0.0 (0x80000000; its own, 0x7fffffff, stays unused): the two compare equal, in `score >= thresh` and in
+// torch.topk, so between them the lower index decides, not the sign.  score_of turns that key back into +0.0.
 __device__ __forceinline__ uint32_t key_of(float f) {
     const uint32_t u = __float_as_uint(f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
+    if (u == 0x80000000u) return u;
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float score_of(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }

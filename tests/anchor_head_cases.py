@@ -18,6 +18,9 @@ not from the kernels.  The rectangle geometry and the greedy walk are center_hea
   select_ref     the score mask (>=), the top pre_max in descending order, equal scores towards the lower anchor index, NaNs first
   head_final     per scene: select, the greedy walk over the fp64 IoU, the post-NMS cut, labels + 1
   margins        the distances the cases keep from every decision that fp32 kernels could take the other way
+  edge cases     DECODE_EDGE_SHAPES (the tile widths of k_anchor_decode), DIR_PARAMS / dir_bin_case (direction bins), signed_case /
+                 k_sizes_case / spliced_list (lvq_anchor_select), empty_scene_input: what tests/test_gpu_anchor_head_edges.py runs;
+                 tests/test_head_edges_conditions.py asserts on the CPU that each reaches its route and pins the older cases' streams
 
 The seeds below were chosen (tools/make_anchor_head_golden.py --search) so that every margin condition holds;
 tests/test_anchor_head_restatements.py asserts them on the CPU.
@@ -220,8 +223,9 @@ def select_ref(scores, thresh, pre_max):
     sc = np.asarray(scores, np.float32)
     with np.errstate(invalid="ignore"):
         idx = np.nonzero(sc >= np.float32(thresh))[0] if thresh is not None else np.arange(sc.size)
-    key = np.where(np.isnan(sc[idx]), np.inf, sc[idx].astype(np.float64))
-    return idx[np.lexsort((idx, -key))][:pre_max]
+    nan = np.isnan(sc[idx])                                                      # above +inf, as torch.topk has it
+    key = np.where(nan, np.inf, sc[idx].astype(np.float64))
+    return idx[np.lexsort((idx, -key, ~nan))][:pre_max]
 
 
 def head_final(dec, post):
@@ -294,6 +298,19 @@ def case_ref(name, xseed=None):
     return maps64, dec, head_final(dec, case_post(name))
 
 
+def case_ref_x(name, x):
+    """case_ref for an explicit input [B, C, H, W] (not cached)."""
+    maps64 = head_maps(name, x)
+    dec = decode_ref(f32(maps64[0]), f32(maps64[1]), f32(maps64[2]), anchors_ref(name).astype(np.float32), n_anchors(name))
+    return maps64, dec, head_final(dec, case_post(name))
+
+
+def empty_scene_input(name):
+    """[3, C, H, W]: the case's two scenes around a scene of zeros, whose logits are the cls biases."""
+    x = case_input(name)
+    return np.stack([x[0], np.zeros_like(x[0]), x[1]])
+
+
 # --------------------------------------------------------------------------------------------------------------------------------
 # kernel cases: decode
 # --------------------------------------------------------------------------------------------------------------------------------
@@ -303,12 +320,13 @@ DECODE_SEED = 701
 
 
 @functools.lru_cache(maxsize=None)
-def decode_case(b, h, w, a, n_cls, use_dir):
+def decode_case(b, h, w, a, n_cls, use_dir, n_dir_bins=NUM_DIR_BINS):
     """(maps [B, c_total, H, W] fp32 with cls | box | dir side by side, anchors [H W A, 7] fp32, (cls, box, dir) first channels).  Logits
     N(0, 2); centre residuals N(0, 0.5), size residuals N(0, 0.3), heading residuals N(0, 0.7); anchors on a 0.8 m grid with sizes of
-    1 .. 4 m and rotations 0 / 1.57 in turn."""
+    1 .. 4 m and rotations 0 / 1.57 in turn.  The direction logits are drawn behind the other maps and in front of the anchors' heights and sizes: another n_dir_bins leaves the
+    cls and box maps as they are and moves the anchors; with the default every value is where it was."""
     rng = np.random.default_rng(DECODE_SEED + 7 * h + w + a)
-    c_cls, c_box, c_dir = a * n_cls, a * 7, a * NUM_DIR_BINS if use_dir else 0
+    c_cls, c_box, c_dir = a * n_cls, a * 7, a * n_dir_bins if use_dir else 0
     maps = np.zeros((b, c_cls + c_box + c_dir + 3, h, w), np.float32)         # three spare channels behind, as a padded conv leaves them
     maps[:, :c_cls] = rng.standard_normal((b, c_cls, h, w)) * 2.0
     spread = np.tile([0.5, 0.5, 0.5, 0.3, 0.3, 0.3, 0.7], a).reshape(1, -1, 1, 1)
@@ -324,9 +342,60 @@ def decode_case(b, h, w, a, n_cls, use_dir):
     return maps, anchors.reshape(-1, 7), (0, c_cls, c_cls + c_box if use_dir else -1)
 
 
-def decode_case_ref(b, h, w, a, n_cls, use_dir):
-    maps, anchors, (c0, c1, c2) = decode_case(b, h, w, a, n_cls, use_dir)
-    return decode_ref(maps[:, c0:c0 + a * n_cls], maps[:, c1:c1 + a * 7], maps[:, c2:c2 + a * NUM_DIR_BINS] if use_dir else None, anchors, a)
+def decode_case_ref(b, h, w, a, n_cls, use_dir, n_dir_bins=NUM_DIR_BINS, dir_offset=DIR_OFFSET, dir_limit_offset=DIR_LIMIT_OFFSET, maps=None):
+    """decode_ref of a decode case; maps: an edited copy of the case's maps."""
+    m, anchors, (c0, c1, c2) = decode_case(b, h, w, a, n_cls, use_dir, n_dir_bins)
+    m = m if maps is None else maps
+    return decode_ref(m[:, c0:c0 + a * n_cls], m[:, c1:c1 + a * 7], m[:, c2:c2 + a * n_dir_bins] if use_dir else None, anchors, a,
+                      dir_offset, dir_limit_offset)
+
+
+# The tile of k_anchor_decode: 64 pixels, halved while px * A * (n_cls + 10) words + 16 bytes exceed 48 KB (include/lvq.h: a pixel's
+# anchors must fit, n_anchors * (n_cls + 10) <= 12284).  Written from the header's rule, not read from the kernel.
+DECODE_LDS = 48 * 1024
+
+
+def decode_tile_bytes(px, a, n_cls):
+    return px * a * (n_cls + 10) * 4 + 16
+
+
+def decode_px(a, n_cls):
+    """The pixels per workgroup that the 48 KB rule leaves, or None where one pixel's anchors do not fit (the call is refused)."""
+    px = 64
+    while px > 1 and decode_tile_bytes(px, a, n_cls) > DECODE_LDS:
+        px //= 2
+    return px if decode_tile_bytes(px, a, n_cls) <= DECODE_LDS else None
+
+
+# (B, H, W, A, n_cls, dir?) -> the px it forces.  The last one is there for its output offsets: with N = 3 the box runs of scenes 0 .. 3
+# start at (b * N) * 7 = 0, 21, 42, 63 words: every residue mod 4 of store_run's scalar head.
+DECODE_EDGE_SHAPES = {(2, 3, 11, 12, 6, True): 32, (1, 5, 7, 20, 10, True): 16, (1, 2, 9, 40, 20, False): 8, (1, 1, 5, 83, 64, True): 2,
+                      (1, 1, 3, 166, 64, True): 1, (4, 1, 3, 1, 2, True): 64}
+DECODE_ON_THE_LIMIT = [(83, 64, 2), (166, 64, 1)]         # (A, n_cls, px): the tile is exactly 48 KB
+DECODE_REFUSED = (167, 64)
+# (n_dir_bins, dir_limit_offset, dir_offset) at DIR_SHAPE; the last is the parameters of every other case
+DIR_SHAPE = (2, 5, 7, 6, 3, True)
+DIR_PARAMS = [(4, 0.5, 0.0), (3, 0.5, 0.78539), (2, 0.0, 0.78539)]
+CAND_SHAPES = [(3, 5, 7, 6, 3, True), (3, 5, 7, 20, 10, True)]      # px 64 (one ragged tile of 35 pixels) and px 16 (16, 16, 3)
+
+
+def decode_run_starts(shape, px):
+    """The first word of every (scene, tile) run of box_preds: (b * N + n0) * 7."""
+    b, h, w, a = shape[:4]
+    return [(s * h * w * a + p0 * a) * 7 for s in range(b) for p0 in range(0, h * w, px)]
+
+
+def dir_bin_case(rule):
+    """DIR_SHAPE with 4 bins and scene 0's direction logits of anchor 1 rewritten at every pixel -> (maps, the bin every such anchor must take).
+    rule: 'tie' two equal top logits (bins 1 and 3), 'nan0' a NaN in bin 0, 'nan2' a NaN in bin 2 below a larger finite logit in bin 3,
+    'nan13' NaNs in bins 1 and 3."""
+    b, h, w, a, n_cls, _ = DIR_SHAPE
+    maps, _, (_, _, c2) = decode_case(*DIR_SHAPE, 4)
+    maps = maps.copy()
+    logits, want = dict(tie=([0.25, 1.5, -0.5, 1.5], 1), nan0=([np.nan, 3.0, 1.0, 2.0], 0), nan2=([0.5, 1.0, np.nan, 7.0], 2),
+                        nan13=([2.0, np.nan, 0.0, np.nan], 1))[rule]
+    maps[0, c2 + 4:c2 + 8] = np.asarray(logits, np.float32).reshape(4, 1, 1)
+    return maps, want
 
 
 # --------------------------------------------------------------------------------------------------------------------------------
@@ -384,6 +453,115 @@ def select_case(name):
     for a in (scores, labels, boxes):
         a.setflags(write=False)
     return scores, labels, boxes, pre_max, SELECT_THRESH if has_thresh else None
+
+
+# Signed scores, as lvq_anchor_select may get them from elsewhere.  select_scene's stream is not touched: these have their own builder.
+SIGNED_N, SIGNED_SEED = 3000, 851
+SIGNED_ZEROS = dict(neg=(3, 12, 16, 1500, 2998), pos=(10, 14, 15, 900, 2100))      # -0.0 sits at the lowest and at the highest index
+FLT_MAX = np.finfo(np.float32).max
+K_SIZES_N, K_SIZES_SURVIVORS, K_SIZES = 20000, 5000, (1, 2, 3, 4095, 4096)         # the bitonic sort runs over 2, 2, 4, 4096, 4096
+
+
+def signed_scene(rng, n=SIGNED_N):
+    """[n] fp32 drawn from N(0, 3), different and non-zero, with planted values: -0.0 and +0.0 five times each at interleaved anchors,
+    +-inf, the smallest denormals of both signs, -FLT_MAX, three NaNs with a clear and three with a set sign bit."""
+    sc = rng.standard_normal(n).astype(np.float32) * np.float32(3.0)
+    assert len(np.unique(sc)) == n and not (sc == 0).any()
+    bits = sc.view(np.uint32)
+    free = [int(c) for c in rng.permutation(n) if c not in SIGNED_ZEROS["neg"] + SIGNED_ZEROS["pos"]]
+    for cell in SIGNED_ZEROS["neg"]:
+        bits[cell] = 0x80000000
+    for cell in SIGNED_ZEROS["pos"]:
+        bits[cell] = 0
+    for cell, v in zip(free, (np.inf, -np.inf, 1e-45, -1e-45, -FLT_MAX)):
+        sc[cell] = np.float32(v)
+    for j, cell in enumerate(free[5:11]):
+        bits[cell] = (0x7fc00000, 0xffc00000)[j % 2]
+    return sc
+
+
+def signed_cut(scores, thresh):
+    """A pre_max that ends inside the +-0 block: everything in front of the zeros (NaNs without a threshold, the positive scores), and four
+    of the ten zeros."""
+    with np.errstate(invalid="ignore"):
+        front = (scores > 0) | (np.isnan(scores) if thresh is None else False)
+    per_scene = front.sum(1)
+    assert len(set(per_scene.tolist())) == 1, "both scenes must have the zeros at the same place"
+    return int(per_scene[0]) + 4
+
+
+@functools.lru_cache(maxsize=None)
+def signed_case():
+    """(scores [2, N] fp32, labels, boxes): scene 1 holds scene 0's values at other anchors, except the zeros, which stay where they are."""
+    rng = np.random.default_rng(SIGNED_SEED)
+    s0 = signed_scene(rng)
+    zeros = np.array(SIGNED_ZEROS["neg"] + SIGNED_ZEROS["pos"])
+    rest = np.setdiff1d(np.arange(SIGNED_N), zeros)
+    s1 = s0.copy()
+    s1.view(np.uint32)[rest] = s0.view(np.uint32)[rng.permutation(rest)]
+    scores = np.stack([s0, s1])
+    labels = rng.integers(0, 3, scores.shape).astype(np.int32)
+    boxes = rng.standard_normal(scores.shape + (7,)).astype(np.float32)
+    for a in (scores, labels, boxes):
+        a.setflags(write=False)
+    return scores, labels, boxes
+
+
+@functools.lru_cache(maxsize=None)
+def k_sizes_case():
+    rng = np.random.default_rng(SIGNED_SEED + 1)
+    scores = np.stack([select_scene(rng, K_SIZES_N, K_SIZES_SURVIVORS), select_scene(rng, K_SIZES_N, K_SIZES_SURVIVORS)])
+    labels = rng.integers(0, 3, scores.shape).astype(np.int32)
+    boxes = rng.standard_normal(scores.shape + (7,)).astype(np.float32)
+    for a in (scores, labels, boxes):
+        a.setflags(write=False)
+    return scores, labels, boxes
+
+
+def select_edge_variants(name):
+    """name -> (scores, labels, boxes, [(thresh, pre_max)]).  signed_thresh puts -0.0 ON the threshold 0.0 (-0.0 >= 0.0 holds)."""
+    if name == "k_sizes":
+        return k_sizes_case() + ([(SELECT_THRESH, k) for k in K_SIZES],)
+    scores, labels, boxes = signed_case()
+    if name == "signed_no_thresh":
+        return scores, labels, boxes, [(None, 50), (None, signed_cut(scores, None)), (None, 4096)]
+    assert name == "signed_thresh"
+    cut = signed_cut(scores, 0.0)
+    return scores, labels, boxes, [(-1.5, 50), (-1.5, cut), (-1.5, 4096), (0.0, 50), (0.0, cut), (0.0, 4096)]
+
+
+SELECT_EDGE_CASES = ("signed_no_thresh", "signed_thresh", "k_sizes")
+
+
+def documented_keys(scores):
+    """The order of include/lvq.h as unsigned keys, written from the header: every NaN on top, the floats in their order below, -0.0 with +0.0."""
+    u = np.ascontiguousarray(scores, np.float32).view(np.uint32).astype(np.int64)
+    mag = u & 0x7fffffff
+    key = np.where(u >> 31 == 1, 0xffffffff - u, u | 0x80000000)
+    key = np.where(mag == 0, 0x80000000, key)
+    return np.where(mag > 0x7f800000, 0xffffffff, key)
+
+
+def select_by_keys(scores, thresh, pre_max):
+    """select_ref from documented_keys: the mask in fp32, then (key descending, index ascending)."""
+    sc = np.asarray(scores, np.float32)
+    with np.errstate(invalid="ignore"):
+        idx = np.nonzero(sc >= np.float32(thresh))[0] if thresh is not None else np.arange(sc.size)
+    return idx[np.lexsort((idx, -documented_keys(sc[idx])))][:pre_max]
+
+
+def spliced_list(scores, thresh, rng, fill):
+    """A candidate list [N] int32 for one scene: its survivors, with entries that take no part spliced in (-1, n, n + 7, 2^31 - 1 and up to
+    twenty anchors below the threshold), shuffled; `fill` behind them.  -> (list, the number of entries in front of the fill)."""
+    n = scores.size
+    with np.errstate(invalid="ignore"):
+        ok = scores >= np.float32(thresh)
+    below = rng.permutation(np.nonzero(~ok)[0])[:20]
+    entries = rng.permutation(np.concatenate([np.nonzero(ok)[0], below, [-1, n, n + 7, 2 ** 31 - 1]]).astype(np.int64))
+    assert len(entries) <= n
+    out = np.full(n, fill, np.int32)
+    out[:len(entries)] = entries
+    return out, len(entries)
 
 
 # --------------------------------------------------------------------------------------------------------------------------------

@@ -54,40 +54,8 @@ SIZES = [(1, 1, 1), (63, 1, 3), (64, 1, 6), (65, 1, 1), (200, 1, 6), (1, 9, 3), 
 
 @functools.lru_cache(maxsize=None)
 def head_case(n, kvol, n_tasks, seed=11):
-    """Operands of one lvq_sparse_head call and its fp64 result [16 T, n]."""
-    rng = np.random.default_rng([seed, n, kvol, n_tasks])
-    widths = LAYOUTS[:n_tasks]
-    bs = max(len(w) for w in widths)
-    feat = rng.standard_normal((n, C)).astype(np.float32)
-    nbr = None
-    if kvol == 9:
-        nbr = np.where(rng.random((n, 9)) < 0.6, rng.integers(0, n, (n, 9)), -1).astype(np.int32)
-        nbr[:, 4] = np.arange(n)
-        bad = rng.random((n, 9)) < 0.08                                          # out-of-range entries read as absent
-        bad[:, 4] = False
-        nbr[bad] = rng.choice(np.array([n, n + 5, -7, 2 ** 31 - 1], np.int64), int(bad.sum())).astype(np.int32)
-    w1 = (rng.standard_normal((n_tasks, bs, C, kvol, C)) * np.sqrt(2.0 / (C * max(1.0, 0.6 * kvol)))).astype(np.float32)     # [C_out, K, C_in]
-    scale = (1.0 + 0.1 * rng.standard_normal((n_tasks, bs, C))).astype(np.float32)
-    shift = (0.1 * rng.standard_normal((n_tasks, bs, C))).astype(np.float32)
-    w_last = (rng.standard_normal((n_tasks, TASK_C, C)) / np.sqrt(C)).astype(np.float32)
-    bias = rng.standard_normal((n_tasks, TASK_C)).astype(np.float32)
-    owner = [sum(([j] * w for j, w in enumerate(ws)), []) for ws in widths]
-    owner = [o + [-1] * (TASK_C - len(o)) for o in owner]
-    ref = np.zeros((TASK_C * n_tasks, n))
-    table = np.arange(n).reshape(n, 1) if nbr is None else np.where((nbr >= 0) & (nbr < n), nbr, -1)
-    f64 = feat.astype(np.float64)
-    for ti, ws in enumerate(widths):
-        for j in range(len(ws)):
-            mid = np.zeros((n, C))
-            for o in range(kvol):
-                g = np.where((table[:, o] >= 0)[:, None], f64[np.maximum(table[:, o], 0)], 0.0)
-                mid += g @ w1[ti, j, :, o].astype(np.float64).T
-            mid = np.maximum(mid * scale[ti, j] + shift[ti, j], 0.0)
-            for c in range(TASK_C):
-                if owner[ti][c] == j:
-                    ref[TASK_C * ti + c] = mid @ w_last[ti, c].astype(np.float64) + bias[ti, c]
-    return dict(feat=feat, nbr=nbr, w1=w1, scale=scale, shift=shift, w_last=w_last, bias=bias, owner=owner, n_br=[len(w) for w in widths],
-                bs=bs, ref=ref)
+    """Operands of one lvq_sparse_head call and its fp64 result [16 T, n] (voxelnext_head_cases.sparse_head_case, seeded per size)."""
+    return VC.sparse_head_case(np.random.default_rng([seed, n, kvol, n_tasks]), LAYOUTS[:n_tasks], n, kvol)
 
 
 def pack(w1, split):
@@ -178,75 +146,63 @@ def test_sparse_head_num_conv_1_and_argument_errors():
 # ---------------------------------------------------------------------------------------------------------------------------------
 WIDE = [-1e3, -1e3, -1e3, 1e3, 1e3, 1e3]
 CUT = [-2.8, -10.0, -10.0, 2.8, 10.0, 10.0]                                      # an 8 x 8 grid of 0.8 m cells spans +-3.2 m
-NAMES = ("center", "center_z", "dim", "rot", "vel", "hm")
+NAMES = VC.DECODE_NAMES
 
 
 def rows_case(n_rows, n_cls, vel, seed, grid=8, interleave=True, extra_b=None):
     """Scenes with n_rows[s] rows each on a grid x grid map, interleaved; extra_b: rows with that batch index appended in between."""
     rng = np.random.default_rng(seed)
-    idx = []
-    for s, m in enumerate(n_rows):
-        cells = rng.permutation(grid * grid)[:m]
-        idx += [(s, int(c) // grid, int(c) % grid) for c in cells]
-    if extra_b is not None:
-        idx += [(extra_b, 1, 1), (extra_b, 2, 5), (-1, 3, 3)]
-    idx = np.array(idx, np.int32).reshape(-1, 3)
-    if interleave and len(idx):
-        idx = idx[rng.permutation(len(idx))]
-    n = len(idx)
-    task = dict(hm=rng.uniform(-5.0, 1.0, (n, n_cls)).astype(np.float32), center=rng.uniform(0, 1, (n, 2)).astype(np.float32),
-                center_z=rng.normal(size=(n, 1)).astype(np.float32), dim=rng.normal(-0.5, 0.3, (n, 3)).astype(np.float32),
-                rot=rng.normal(size=(n, 2)).astype(np.float32))
-    if vel:
-        task["vel"] = rng.normal(size=(n, 2)).astype(np.float32)
-    return idx, task
+    extra = [(extra_b, 1, 1), (extra_b, 2, 5), (-1, 3, 3)] if extra_b is not None else []
+    idx = VC.scene_rows(rng, n_rows, grid, extra, interleave)
+    return idx, VC.task_rows(rng, len(idx), n_cls, vel)
 
 
 def head_buffer(task, n_cls):
     """one task's rows -> (channel-major [16, N] buffer, task_channels row)"""
-    n = len(task["hm"])
-    buf = np.zeros((TASK_C, n), np.float32)
-    chans, o = [], 0
-    for name in NAMES:
-        if name in task:
-            w = task[name].shape[1]
-            buf[o:o + w] = task[name].T
-            chans.append(o)
-            o += w
-        else:
-            chans.append(-1)
-    return buf, chans
+    buf, chans = VC.head_buffer([task])
+    return buf, chans[0]
+
+
+def check_decode_tasks(idx, tasks, batch, k, thresh, limit, ids, stride=4, voxel=(0.2, 0.2), origin=(-3.2, -3.2), margins=True):
+    """ONE lvq_voxel_decode over all `tasks` (ids: per task its class ids) against decode_ref per task: counts, labels and order exact,
+    scores and boxes within 1e-5 relative, rows behind a count zeros.  -> ([task][scene] rows seen, [task][scene] decode_ref dicts)."""
+    buf, chans = VC.head_buffer(tasks)
+    dim = 9 if "vel" in tasks[0] else 7
+    n_cls = [t["hm"].shape[1] for t in tasks]
+    boxes, scores, labels, counts = ops.voxel_decode(dev(buf), dev(idx, np.int32), batch, chans, n_cls, [c for row in ids for c in row], k=k,
+                                                     box_dim=dim, stride=stride, voxel_xy=list(voxel), range_xy=list(origin), limit_range=limit,
+                                                     score_thresh=thresh)
+    boxes, scores, labels, counts = boxes.cpu().numpy(), scores.cpu().numpy(), labels.cpu().numpy(), counts.cpu().numpy()
+    assert boxes.shape == (batch, len(tasks), k, dim) and counts.shape == (batch, len(tasks))
+    seen, refs = [], []
+    for t, task in enumerate(tasks):
+        ref = VC.decode_ref(task, idx, batch, k, stride, voxel, origin, limit, thresh, ids[t])
+        seen.append([])
+        refs.append(ref)
+        for s, d in enumerate(ref):
+            if margins and len(d["cand_scores"]):
+                distinct, _, near_thresh, near_limit = VC.decode_margins(d, min(k, len(d["cand_boxes"])), limit, thresh)
+                assert distinct >= 4 and near_thresh >= 1e-4 and near_limit >= 1e-3, (t, s, distinct, near_thresh, near_limit)
+            n = len(d["scores"])
+            seen[t].append(n)
+            assert counts[s, t] == n, (t, s, counts[s, t], n)
+            assert np.array_equal(labels[s, t, :n], d["labels"]), (t, s)
+            if n:
+                ok = ~np.isnan(d["scores"])
+                assert np.array_equal(np.isnan(scores[s, t, :n]), ~ok)
+                rel_s = np.abs(scores[s, t, :n] - d["scores"])[ok] / d["scores"][ok]
+                scale = np.maximum(np.abs(d["boxes"]), 1e-2)
+                scale[:, 0], scale[:, 1] = np.maximum(scale[:, 0], abs(origin[0])), np.maximum(scale[:, 1], abs(origin[1]))
+                rel_b = np.abs(boxes[s, t, :n] - d["boxes"]) / scale
+                print(f"task {t} scene {s}: {n} of {k} (n_b {d['n_b']}); scores {rel_s.max(initial=0):.2e}, boxes {rel_b.max():.2e}")
+                assert rel_s.max(initial=0) <= 1e-5 and rel_b.max() <= 1e-5
+            assert not boxes[s, t, n:].any() and not scores[s, t, n:].any() and not labels[s, t, n:].any()      # rows behind the count are zeros
+    return seen, refs
 
 
 def check_decode(idx, task, batch, k, thresh, limit, ids, stride=4, voxel=(0.2, 0.2), origin=(-3.2, -3.2), margins=True):
-    n_cls = task["hm"].shape[1]
-    buf, chans = head_buffer(task, n_cls)
-    dim = 9 if "vel" in task else 7
-    boxes, scores, labels, counts = ops.voxel_decode(dev(buf), dev(idx, np.int32), batch, [chans], [n_cls], ids, k=k, box_dim=dim, stride=stride,
-                                                     voxel_xy=list(voxel), range_xy=list(origin), limit_range=limit, score_thresh=thresh)
-    boxes, scores, labels, counts = boxes.cpu().numpy(), scores.cpu().numpy(), labels.cpu().numpy(), counts.cpu().numpy()
-    assert boxes.shape == (batch, 1, k, dim)
-    ref = VC.decode_ref(task, idx, batch, k, stride, voxel, origin, limit, thresh, ids)
-    seen = []
-    for s, d in enumerate(ref):
-        if margins and len(d["cand_scores"]):
-            distinct, _, near_thresh, near_limit = VC.decode_margins(d, min(k, len(d["cand_boxes"])), limit, thresh)
-            assert distinct >= 4 and near_thresh >= 1e-4 and near_limit >= 1e-3, (s, distinct, near_thresh, near_limit)
-        n = len(d["scores"])
-        seen.append(n)
-        assert counts[s, 0] == n, (s, counts[s, 0], n)
-        assert np.array_equal(labels[s, 0, :n], d["labels"]), s
-        if n:
-            ok = ~np.isnan(d["scores"])
-            assert np.array_equal(np.isnan(scores[s, 0, :n]), ~ok)
-            rel_s = np.abs(scores[s, 0, :n] - d["scores"])[ok] / d["scores"][ok]
-            scale = np.maximum(np.abs(d["boxes"]), 1e-2)
-            scale[:, 0], scale[:, 1] = np.maximum(scale[:, 0], abs(origin[0])), np.maximum(scale[:, 1], abs(origin[1]))
-            rel_b = np.abs(boxes[s, 0, :n] - d["boxes"]) / scale
-            print(f"scene {s}: {n} of {k} (n_b {d['n_b']}); scores {rel_s.max(initial=0):.2e}, boxes {rel_b.max():.2e}")
-            assert rel_s.max(initial=0) <= 1e-5 and rel_b.max() <= 1e-5
-        assert not boxes[s, 0, n:].any() and not scores[s, 0, n:].any() and not labels[s, 0, n:].any()      # rows behind the count are zeros
-    return seen, ref
+    seen, refs = check_decode_tasks(idx, [task], batch, k, thresh, limit, [ids], stride, voxel, origin, margins)
+    return seen[0], refs[0]
 
 
 def test_decode_interleaved_scenes():

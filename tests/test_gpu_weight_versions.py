@@ -8,7 +8,9 @@ No tolerance anywhere: a module whose weights were changed in place must return 
                One tensor of every group of parameters in turn; a "mixed" -> "bf16" -> "mixed" excursion; growth of the K|V buffers.
   StandInHead  cases.HEAD_CASE (the smallest tests/test_gpu_head.py builds): one member of a packed q|k|v group.
   PillarVFE    the first single-layer case of tests/lidar_feature_cases.py with USE_NORM (33 pillars, T = 1, 4 -> 8): the BatchNorm fold.
-  CenterHead   the "single" case of tests/center_head_cases.py: the fused first and block-diagonal last convs are packed from several containers."""
+  CenterHead   the "single" case of tests/center_head_cases.py: the fused first and block-diagonal last convs are packed from several containers.
+  AnchorHeadSingle   the "kitti" case of tests/anchor_head_cases.py: the one fused 1 x 1 conv and the flattened anchors.
+  VoxelNeXtHead      the "nusc" case of tests/voxelnext_head_cases.py: packed first convs, folded norms and last convs of 36 branches."""
 import pytest
 import torch
 
@@ -214,3 +216,107 @@ def test_center_head_repacks_its_fused_convs(monkeypatch):
     assert not torch.equal(loaded, changed2)
     settled(m, loaded)
     assert torch.equal(maps(_center_head(other)), loaded)
+
+
+def _anchor_head(sd):
+    import numpy as np
+    import anchor_head_cases as AC
+    from lidar_vision_vqa_amd import anchor_head as AH
+    c = AC.MODULE_CASES["kitti"]
+    m = AH.AnchorHeadSingle(AC.case_cfg("kitti"), c["shape"][1], len(c["class_names"]), c["class_names"], np.array(c["grid_size"]),
+                            c["point_cloud_range"])
+    m.load_state_dict(sd, strict=True)
+    return m.to(DEV).eval()
+
+
+def test_anchor_head_repacks_its_fused_conv_and_rebuilds_its_anchors(monkeypatch):
+    import anchor_head_cases as AC
+    from lidar_vision_vqa_amd import ops
+    x = TK.dev(AC.case_input("kitti"))
+    calls = []
+    real = ops.conv2d_pack_weights
+    monkeypatch.setattr(ops, "conv2d_pack_weights", lambda *a, **k: (calls.append(1), real(*a, **k))[1])
+
+    def dense(m):
+        with torch.no_grad():
+            out = m(dict(spatial_features_2d=x, batch_size=x.shape[0]))
+        return torch.cat([out["batch_cls_preds"], out["batch_box_preds"]], dim=-1).clone()
+
+    def settled(m, want):
+        n = len(calls)
+        assert torch.equal(dense(m), want) and len(calls) == n, "a forward without a change packed something, or changed its result"
+        assert torch.equal(dense(_anchor_head(m.state_dict())), want), "something derived from the old value is still in use"
+
+    m = _anchor_head({k: torch.from_numpy(v) for k, v in AC.case_state("kitti").items()})
+    before = dense(m)
+    assert len(calls) == 1, "cls | box | dir are ONE fused 1 x 1 conv"
+    settled(m, before)
+    last = before
+    for change in (lambda: m.conv_cls.bias.add_(0.5), lambda: m.conv_box.weight.mul_(1.25),
+                   lambda: m.load_state_dict({k: v * 0.5 for k, v in m.state_dict().items()}, strict=True)):
+        n = len(calls)
+        with torch.no_grad():
+            change()
+        changed = dense(m)
+        assert not torch.equal(changed, last) and len(calls) == n + 1
+        settled(m, changed)
+        last = changed
+    flat = m.flat_anchors()
+    assert m.flat_anchors() is flat
+    with torch.no_grad():
+        m.anchors_0.add_(0.25)
+    n = len(calls)
+    moved = dense(m)
+    assert m.flat_anchors() is not flat and torch.equal(m.flat_anchors(), torch.cat(m.anchors, dim=-3).reshape(-1, 7))
+    assert len(calls) == n and not torch.equal(moved[..., 3:6], last[..., 3:6]) and torch.equal(moved[..., :3], last[..., :3])
+    assert torch.equal(dense(m), moved) and len(calls) == n
+
+
+def _voxelnext_head(sd):
+    import test_gpu_voxelnext_head as TV
+    m = TV.build("nusc")
+    m.load_state_dict(sd, strict=True)
+    return m.to(DEV).eval()
+
+
+def test_voxelnext_head_repacks_its_operands(monkeypatch):
+    import test_gpu_voxelnext_head as TV
+    import voxelnext_head_cases as VC
+    from lidar_vision_vqa_amd import _ffi as F
+    calls = []
+    L = F.lib()
+    real = L.lvq_sparse_conv_pack_weights
+    monkeypatch.setattr(L, "lvq_sparse_conv_pack_weights", lambda *a: (calls.append(1), real(*a))[1])
+
+    def rows(m):
+        _, pred = TV.run(m, TV.tensor("nusc"))
+        return torch.cat([v for d in pred for v in d.values()], dim=1).clone()
+
+    def settled(m, want):
+        n = len(calls)
+        assert torch.equal(rows(m), want) and len(calls) == n, "a forward without a change packed something, or changed its result"
+        assert torch.equal(rows(_voxelnext_head(m.state_dict())), want), "something derived from the old value is still in use"
+
+    m = _voxelnext_head({k: TV.t(v) for k, v in VC.case_state("nusc").items()})
+    n_first = sum(len(h.sep_head_dict) for h in m.heads_list)
+    before = rows(m)
+    assert len(calls) == n_first == 36, "one packed first conv per branch of the six tasks"
+    settled(m, before)
+    with torch.no_grad():
+        m.heads_list[1].dim[-1].weight.mul_(1.25)                  # a branch's last conv: fp32 operands, nothing to pack
+    n = len(calls)
+    changed = rows(m)
+    assert not torch.equal(changed, before) and len(calls) == n
+    settled(m, changed)
+    with torch.no_grad():
+        m.heads_list[2].hm[0][1].running_var.mul_(1.5)             # a BatchNorm buffer: the folded scale and shift
+    n = len(calls)
+    changed2 = rows(m)
+    assert not torch.equal(changed2, changed) and len(calls) == n
+    settled(m, changed2)
+    with torch.no_grad():
+        m.heads_list[0].center[0][0].weight.mul_(0.75)             # a first conv: exactly one branch is packed again
+    n = len(calls)
+    changed3 = rows(m)
+    assert not torch.equal(changed3, changed2) and len(calls) == n + 1
+    settled(m, changed3)

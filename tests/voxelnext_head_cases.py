@@ -293,3 +293,181 @@ def limit_drops(cfg, pre):
 def module_margins(cfg, pre, near):
     """center_head_cases.module_margins over the row-form decode."""
     return CC.module_margins(cfg, pre, near)
+
+
+# --------------------------------------------------------------------------------------------------------------------------------
+# kernel cases the first suite does not reach (tests/test_gpu_voxelnext_head_edges.py; conditions in tests/test_head_edges_conditions.py)
+# --------------------------------------------------------------------------------------------------------------------------------
+TASK_C = 16
+# widths per branch of every task: at most four branches per task, so lvq_sparse_head launches its four-branch kernel
+EDGE_LAYOUTS = {"two": [[4, 1]], "one": [[1]], "three_four": [[2, 1, 3], [2, 1, 3, 2]]}
+EDGE_SIZES = [(name, kvol, n) for name in EDGE_LAYOUTS for kvol in (1, 9) for n in (1, 65, 200)]
+WIDE_PITCH_LAYOUT = [[2, 1, 3, 2, 3], [2, 1, 3, 2, 2]]                           # five branches, operands pitched for eight
+STRUCTURED_OFFSETS = [(0, 4), (4,), (4, 8), tuple(range(9))]                      # rows 0-15, 16-31, 32-47, 48-63 of every 64-row tile
+
+
+def edge_table(kind, n, rng):
+    """[n, 9] int32 neighbour table, the centre (offset 4) always the row itself.  random60: head_case's 60 % fill with out-of-range
+    entries; sparse5: a 5 % fill; structured: STRUCTURED_OFFSETS by the row's place in its tile (neighbours drawn from all rows)."""
+    if kind == "structured":
+        nbr = np.full((n, 9), -1, np.int64)
+        for r in range(n):
+            for o in STRUCTURED_OFFSETS[(r % 64) // 16]:
+                nbr[r, o] = rng.integers(0, n)
+    else:
+        fill = 0.6 if kind == "random60" else 0.05
+        nbr = np.where(rng.random((n, 9)) < fill, rng.integers(0, n, (n, 9)), -1)
+        if kind == "random60":
+            nbr = nbr.astype(np.int32)
+            nbr[:, 4] = np.arange(n)
+            bad = rng.random((n, 9)) < 0.08                                      # out-of-range entries read as absent
+            bad[:, 4] = False
+            nbr[bad] = rng.choice(np.array([n, n + 5, -7, 2 ** 31 - 1], np.int64), int(bad.sum())).astype(np.int32)
+    nbr[:, 4] = np.arange(n)
+    return nbr.astype(np.int32)
+
+
+def tile_lacks(nbr, n):
+    """Per 64-row tile the offsets no row of it has (the kernel skips them), and per (tile, 16-row block) the offsets it lacks."""
+    ok = (nbr >= 0) & (nbr < n)
+    tiles = [[o for o in range(9) if not ok[t:t + 64, o].any()] for t in range(0, n, 64)]
+    blocks = [[[o for o in range(9) if not ok[t + q:min(t + q + 16, t + 64), o].any()] for q in range(0, 64, 16) if t + q < n]
+              for t in range(0, n, 64)]
+    return tiles, blocks
+
+
+def sparse_head_case(rng, widths, n, kvol, bs=None, table="random60"):
+    """Operands of one lvq_sparse_head call and its fp64 result [16 T, n], drawn from rng: THE builder of the kernel cases (the first
+    suite's head_case and edge_head_case below seed it).  widths: per task the output channels of its branches; bs: the branch pitch of
+    the operands (None: the largest branch count; slots behind a task's branches hold values the kernel must not read into its result);
+    table: edge_table's kind for k_vol 9."""
+    n_tasks = len(widths)
+    bs = max(len(w) for w in widths) if bs is None else bs
+    feat = rng.standard_normal((n, C)).astype(np.float32)
+    nbr = edge_table(table, n, rng) if kvol == 9 else None
+    fill = {"random60": 0.6, "sparse5": 0.05, "structured": 0.4}[table]
+    w1 = (rng.standard_normal((n_tasks, bs, C, kvol, C)) * np.sqrt(2.0 / (C * max(1.0, fill * kvol)))).astype(np.float32)     # [C_out, K, C_in]
+    scale = (1.0 + 0.1 * rng.standard_normal((n_tasks, bs, C))).astype(np.float32)
+    shift = (0.1 * rng.standard_normal((n_tasks, bs, C))).astype(np.float32)
+    w_last = (rng.standard_normal((n_tasks, TASK_C, C)) / np.sqrt(C)).astype(np.float32)
+    bias = rng.standard_normal((n_tasks, TASK_C)).astype(np.float32)
+    owner = [sum(([j] * w for j, w in enumerate(ws)), []) for ws in widths]
+    owner = [o + [-1] * (TASK_C - len(o)) for o in owner]
+    ref = np.zeros((TASK_C * n_tasks, n))
+    tbl = np.arange(n).reshape(n, 1) if nbr is None else np.where((nbr >= 0) & (nbr < n), nbr, -1)
+    f64 = feat.astype(np.float64)
+    for ti, ws in enumerate(widths):
+        for j in range(len(ws)):
+            mid = np.zeros((n, C))
+            for o in range(kvol):
+                g = np.where((tbl[:, o] >= 0)[:, None], f64[np.maximum(tbl[:, o], 0)], 0.0)
+                mid += g @ w1[ti, j, :, o].astype(np.float64).T
+            mid = np.maximum(mid * scale[ti, j] + shift[ti, j], 0.0)
+            for c in range(TASK_C):
+                if owner[ti][c] == j:
+                    ref[TASK_C * ti + c] = mid @ w_last[ti, c].astype(np.float64) + bias[ti, c]
+    return dict(feat=feat, nbr=nbr, w1=w1, scale=scale, shift=shift, w_last=w_last, bias=bias, owner=owner, n_br=[len(w) for w in widths],
+                bs=bs, ref=ref)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_head_case(layout, n, kvol, bs=None, table="random60", seed=211):
+    """sparse_head_case for a key of EDGE_LAYOUTS or "wide_pitch"."""
+    widths = WIDE_PITCH_LAYOUT if layout == "wide_pitch" else EDGE_LAYOUTS[layout]
+    rng = np.random.default_rng([seed, n, kvol, len(widths), sorted(list(EDGE_LAYOUTS) + ["wide_pitch"]).index(layout)])
+    return sparse_head_case(rng, widths, n, kvol, bs, table)
+
+
+DECODE_NAMES = ("center", "center_z", "dim", "rot", "vel", "hm")
+
+
+def task_rows(rng, n, n_cls, vel):
+    """One task's branch outputs for n rows, in the order hm, center, center_z, dim, rot, vel."""
+    task = dict(hm=rng.uniform(-5.0, 1.0, (n, n_cls)).astype(np.float32), center=rng.uniform(0, 1, (n, 2)).astype(np.float32),
+                center_z=rng.normal(size=(n, 1)).astype(np.float32), dim=rng.normal(-0.5, 0.3, (n, 3)).astype(np.float32),
+                rot=rng.normal(size=(n, 2)).astype(np.float32))
+    if vel:
+        task["vel"] = rng.normal(size=(n, 2)).astype(np.float32)
+    return task
+
+
+def scene_rows(rng, n_rows, grid, extra=(), interleave=True):
+    """[N, 3] int32 (b, y, x): n_rows[s] distinct cells of a grid x grid map per scene, then the rows `extra`, all shuffled together."""
+    idx = []
+    for s, m in enumerate(n_rows):
+        idx += [(s, int(c) // grid, int(c) % grid) for c in rng.permutation(grid * grid)[:m]]
+    idx = np.array(idx + list(extra), np.int32).reshape(-1, 3)
+    return idx[rng.permutation(len(idx))] if interleave and len(idx) else idx
+
+
+def head_buffer(tasks):
+    """[{branch: [N, c]}] -> (channel-major [16 T, N] fp32 buffer, task_channels): task t's branches from channel 16 t on."""
+    n = len(tasks[0]["hm"])
+    buf = np.zeros((TASK_C * len(tasks), n), np.float32)
+    chans = []
+    for t, task in enumerate(tasks):
+        row, o = [], TASK_C * t
+        for name in DECODE_NAMES:
+            if name in task:
+                wd = task[name].shape[1]
+                buf[o:o + wd] = task[name].T
+                row.append(o)
+                o += wd
+            else:
+                row.append(-1)
+        chans.append(row)
+    return buf, chans
+
+
+MULTI_N_CLS, MULTI_IDS, MULTI_K, MULTI_ROWS = (1, 2, 3), [[7], [2, 9], [4, 0, 5]], 32, (60, 45, 50)
+MULTI_SEED = 343                                # the first from 311 on whose nine (task, scene) groups keep decode_margins' distances
+
+
+@functools.lru_cache(maxsize=None)
+def multi_task_case():
+    """Three tasks of 1, 2 and 3 classes with vel (box_dim 9) on one set of rows: three scenes interleaved on an 8 x 8 grid, with rows of
+    b = batch and b = -1 among them whose scores would win everywhere.  -> (indices [N, 3], tasks)."""
+    rng = np.random.default_rng(MULTI_SEED)
+    idx = scene_rows(rng, MULTI_ROWS, 8, [(3, 1, 1), (3, 2, 5), (-1, 3, 3), (3, 6, 6), (-1, 0, 7)])
+    tasks = [task_rows(rng, len(idx), c, True) for c in MULTI_N_CLS]
+    foreign = (idx[:, 0] < 0) | (idx[:, 0] >= 3)
+    for t in tasks:
+        t["hm"][foreign] = 9.0
+    return idx, tasks
+
+
+PLATEAU_ROWS, PLATEAU_K, PLATEAU_ABOVE, PLATEAU_EQUAL, PLATEAU_LOGIT = (100, 1300, 100), 64, 23, 700, 0.5
+
+
+@functools.lru_cache(maxsize=None)
+def plateau_case():
+    """Scene 1 of 3 has 1300 rows of 2 classes: 23 (row, class) pairs with distinct scores above a plateau of 700 pairs that share one
+    score, everything else far below; K = 64 ends inside the plateau.  The 1500 rows of the three scenes are interleaved, so the kernel's
+    3000 positions (three per thread) carry the other scenes' zero keys between the plateau's members.  -> (indices, task)."""
+    rng = np.random.default_rng(312)
+    idx = scene_rows(rng, PLATEAU_ROWS, 40, [])
+    n = len(idx)
+    task = task_rows(rng, n, 2, False)
+    rows1 = np.nonzero(idx[:, 0] == 1)[0]
+    task["hm"][rows1] = rng.uniform(-6.0, -3.0, (len(rows1), 2)).astype(np.float32)
+    pairs = rng.permutation(2 * len(rows1))
+    high, level = pairs[:PLATEAU_ABOVE], pairs[PLATEAU_ABOVE:PLATEAU_ABOVE + PLATEAU_EQUAL]
+    task["hm"][rows1[high % len(rows1)], high // len(rows1)] = np.linspace(1.0, 2.1, PLATEAU_ABOVE).astype(np.float32)
+    task["hm"][rows1[level % len(rows1)], level // len(rows1)] = PLATEAU_LOGIT
+    return idx, task
+
+
+def plateau_stats(idx, task, scene, k, threads=1024):
+    """(above, equal, need, keys per thread, threads whose range holds a plateau key, foreign positions between the first and the last
+    plateau member) of the select over the n_cls * N positions class * N + stored row."""
+    n = len(idx)
+    sc = scores32(np.asarray(task["hm"]).T).reshape(-1)                           # position class * N + row
+    mine = np.tile(idx[:, 0] == scene, task["hm"].shape[1])
+    kth = np.sort(sc[mine])[::-1][k - 1]
+    above, equal = int((sc[mine] > kth).sum()), int((sc[mine] == kth).sum())
+    chunk = -(-sc.size // threads)
+    level = mine & (sc == kth)
+    where = np.nonzero(level)[0]
+    owners = len(set((where // chunk).tolist()))
+    between = int((~mine[where[0]:where[-1]]).sum())
+    return above, equal, k - above, chunk, owners, between
