@@ -855,6 +855,83 @@ int lvq_nms_bev_wide(const float *boxes, int box_stride, const int32_t *counts, 
                      int32_t *keep, int32_t *keep_count, void *ws, size_t ws_bytes, lvq_stream_t stream);
 
 /* =====================================================================================
+ * TransFusionHead (csrc/transfusion_head.hip): heat-map proposals -> object queries -> (decoder layer on lvq_gemm_bf16 / lvq_attention_bf16 /
+ * lvq_layernorm) -> feed-forward, prediction branches and box decode
+ * ===================================================================================== */
+
+/* The query initialisation of transfusion_head.py:161-185 for every scene in ONE launch (one workgroup per scene).
+ *   maps          [batch, c_total, h, w] fp32: the raw heat-map logits are channels first_channel .. first_channel + n_cls - 1
+ *   heat          sigmoid(logit).  A cell of a class survives when heat == the maximum over its 3 x 3 neighbourhood, compared in the sigmoid
+ *                 domain (a plateau keeps all its equal cells); a border cell never survives (the reference's local_max is zero there).
+ *                 A class whose bit is set in point_class_mask keeps every cell, border included (nuScenes: classes 8, 9; Waymo: 1, 2).
+ *                 A cell that does not survive scores exactly 0.  A NaN heat stays NaN; a cell with a NaN neighbour does not survive.
+ *   outputs       per scene the n_proposals largest of the n_cls * h * w values, descending, EQUAL VALUES TOWARDS THE LOWER FLAT INDEX (the
+ *                 reference's argsort leaves ties open), NaN first: prop_flat [batch, n_proposals] int32 (class = flat / (h w), cell =
+ *                 flat % (h w)), prop_score [batch, n_proposals], and query_heatmap_score [batch, n_cls, n_proposals], the surviving heat
+ *                 of EVERY class at the chosen cell (transfusion_head.py:212-215).
+ * n_proposals <= 1024 and nms_kernel_size == 3 (else LVQ_EUNSUPPORTED); n_proposals > n_cls * h * w, h or w < 3, n_cls > 64, NULL
+ * operands, non-positive sizes, a channel range outside c_total: LVQ_EINVAL; ws below the query: LVQ_EWORKSPACE.  Every refusal happens
+ * before the launch, outputs untouched.  No allocation, stream-ordered; a scene's outputs do not depend on the other scenes. */
+int lvq_heatmap_proposals_workspace_bytes(int batch, int n_cls, int h, int w, size_t *bytes);
+int lvq_heatmap_proposals(const float *maps, int batch, int c_total, int h, int w, int first_channel, int n_cls,
+                          int64_t point_class_mask, int nms_kernel_size, int n_proposals, int32_t *prop_flat, float *prop_score,
+                          float *query_heatmap_score, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* PositionEmbeddingLearned of transfusion_utils.py:10-26 in eval(): pos [n, 2] fp32 -> out [n, d_out] fp32,
+ *   out = W2 relu((W1 pos) * scale + shift) + b2,   W1 [d, 2], W2 [d_out, d] (Conv1d weights without their last axis), b2 [d_out];
+ *   scale / shift [d]: the BatchNorm1d folded by the caller with the first conv's bias, shift = b1 * scale + (beta - mean * scale).
+ * The module itself has d_out = d.  A caller that feeds the embedding to a Linear alone may fold that Linear into W2 / b2 (TransFusionHead's
+ * key table through the K | V projection: d_out = 2 d), so the table of every grid cell comes out of this one launch.
+ * fp32 operands and FMA accumulation in ascending k; a row's bits do not depend on its position or on n.  d a multiple of 4, d and d_out up
+ * to 512, W2 16-byte aligned (else LVQ_EUNSUPPORTED); NULL operands, n, d or d_out <= 0: LVQ_EINVAL; before the launch.  No workspace. */
+int lvq_pos_embed_learned(const float *pos, int64_t n, int d, int d_out, const float *w1, const float *scale, const float *shift, const float *w2,
+                          const float *b2, float *out, lvq_stream_t stream);
+
+/* The object queries of transfusion_head.py:186-204 for lvq_heatmap_proposals' prop_flat, in two launches.
+ *   feat_hi / feat_lo   the shared conv's output planes [batch, h, w, d] bf16 (lvq_conv2d); feat_lo NULL: the plain form, hi alone
+ *   query_feat    [batch, n_proposals, d] fp32 = (hi + lo)[cell] + (class_w[:, class] + class_b): the one-hot Conv1d of class_encoding is a
+ *                 column pick; class_w [d, n_cls], class_b [d]
+ *   query_pos     [batch, n_proposals, 2] fp32 = (cell % y_size + 0.5, cell / y_size + 0.5): THE REFERENCE'S OWN FORMULA -- create_2D_grid
+ *                 (transfusion_head.py:125-135) is an `ij` meshgrid over (x_size, y_size) that predict() indexes with the row-major cell
+ *                 and flips.  On a square grid that is (column + 0.5, row + 0.5); on any other it is not, and it is reproduced as it is.
+ *   query_labels  [batch, n_proposals] int32 = flat / (h w)
+ *   query_pe      [batch, n_proposals, d] fp32 = lvq_pos_embed_learned(query_pos) with the pe_* operands (self_posembed)
+ * d a multiple of 32 up to 512, n_cls <= 64 (else LVQ_EUNSUPPORTED); NULL operands, non-positive sizes: LVQ_EINVAL; before any launch.  An
+ * entry of prop_flat outside 0 .. n_cls h w - 1 is clamped into it, never used as it is. */
+int lvq_transfusion_queries(const lvq_bf16 *feat_hi, const lvq_bf16 *feat_lo, int batch, int h, int w, int d, const int32_t *prop_flat,
+                            int n_proposals, int n_cls, int y_size, const float *class_w, const float *class_b, const float *pe_w1,
+                            const float *pe_scale, const float *pe_shift, const float *pe_w2, const float *pe_b2, float *query_feat,
+                            float *query_pos, int32_t *query_labels, float *query_pe, lvq_stream_t stream);
+
+/* with_pos_embed of transfusion_utils.py:64-65 as a GEMM operand: hi (+ lo, or NULL) = bf16 parts of x + pe, n elements each. */
+int lvq_transfusion_add_pe(const float *x, const float *pe, int64_t n, lvq_bf16 *hi, lvq_bf16 *lo, lvq_stream_t stream);
+
+/* The rest of the decoder layer and the head for the batch * n_proposals query rows (transfusion_utils.py:95-97; transfusion_head.py:15-49,
+ * 209-210, 397-479), fp32 operands and FMA accumulation in ascending k throughout (no bf16 rounding: the bits do not depend on a precision mode).
+ *   x             [batch, n_proposals, 128] fp32: the output of norm2
+ *   ffn           y = norm3(x + W2 relu(W1 x + b1) + b2): w1 [ffn, 128], w2 [128, ffn], gamma / beta [128], centred statistics
+ *   branches      center (2), height (1), dim (3), rot (2), vel (2, with has_vel), heatmap (n_cls), in this order: head_w1 [nb * 64, 128]
+ *                 with head_scale / head_shift [nb * 64] (the folded BatchNorm1d and conv bias) and ReLU; head_w2 [c_total, 64] whose row o
+ *                 reads the 64 features of o's branch, head_b2 [c_total]; c_total = (has_vel ? 10 : 8) + n_cls
+ *   raw           [batch, c_total, n_proposals] fp32, the reference's res_layer channel-major; `center` already carries + query_pos
+ *   decode        score = sigmoid(heatmap[label]) * prop_score, label = query_labels (the reference takes the argmax of a product with a
+ *                 one-hot, which is the query's class whenever the score is not 0); x = (center_x * stride) * voxel_xy[0] + range_xy[0] (y
+ *                 alike), each product rounded to fp32 in that order; dim = exp; heading = atan2(rot[0], rot[1]) -- channel 0 is the SINE;
+ *                 a row stays when score > score_thresh (strict) and limit_range[0..2] <= (x, y, z) <= limit_range[3..5]
+ *   outputs       boxes [batch, n_proposals, 9 or 7], scores, labels int32 (query class + 1), counts [batch] int32: the kept rows IN
+ *                 PROPOSAL ORDER, zeros behind a count.  voxel_xy / range_xy / limit_range are HOST arrays.
+ * Two launches: 8 rows per workgroup, then one workgroup per scene for the order-keeping compaction (a row's rank is a prefix over its
+ * scene).  n_proposals <= 1024, ffn a multiple of 64 up to 512, n_cls <= 64, 16-byte aligned weights (else LVQ_EUNSUPPORTED); NULL
+ * operands, non-positive sizes: LVQ_EINVAL; ws below the query: LVQ_EWORKSPACE; all before any launch, outputs untouched. */
+int lvq_transfusion_tail_workspace_bytes(int batch, int n_proposals, int box_dim, size_t *bytes);
+int lvq_transfusion_tail(const float *x, const float *query_pos, const int32_t *query_labels, const float *prop_score, int batch,
+                         int n_proposals, int ffn, int n_cls, int has_vel, const float *w1, const float *b1, const float *w2, const float *b2,
+                         const float *gamma, const float *beta, float eps, const float *head_w1, const float *head_scale,
+                         const float *head_shift, const float *head_w2, const float *head_b2, int stride, const float *voxel_xy,
+                         const float *range_xy, const float *limit_range, float score_thresh, float *raw, float *boxes, float *scores,
+                         int32_t *labels, int32_t *counts, void *ws, size_t ws_bytes, lvq_stream_t stream);
+
+/* =====================================================================================
  * Decode-step runtime
  * ===================================================================================== */
 

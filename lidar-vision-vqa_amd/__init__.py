@@ -9,6 +9,8 @@ directory, whose on-disk name carries a hyphen).  Sub-packages:
               registry of both heads, dense_heads_all
   anchor_head AnchorHeadSingle (BEV features -> a box for every anchor: one fused 1 x 1 conv, anchor decode) and post_processing (score mask,
               top 4096, rotated BEV NMS over 64 mask words), the detectors' class-agnostic route; dense_heads_all with all three heads
+  transfusion_head TransFusionHead (BEV features -> heat-map proposals -> one decoder layer over the H W key stream -> 3-D boxes: proposals,
+              query gather, learned position embeddings, fused FFN + branches + decode) ; dense_heads_all with all four heads
   fusion  VATBlock / VATLiDAR / VATVision / VisionAdapter with the reference's nn.Module API
   vision_tower  the SAM ViT image encoder (ImageEncoderViT, build_sam_vit_b) with the reference's nn.Module API
   head    prefix assembly + stand-in decoder head

@@ -1,4 +1,4 @@
-// csrc/head_common.h -- what the dense heads' post-processing kernels share (center_head.hip, anchor_head.hip): the order of fp32
+// csrc/head_common.h -- what the dense heads' post-processing kernels share (center_head.hip, anchor_head.hip, transfusion_head.hip): the order of fp32
 // scores as unsigned keys, the radix select + bitonic sort of the K best candidates, rotated rectangles and their IoU, and the two
 // kernels of the rotated BEV NMS.  Sizes are template parameters: THREADS is the workgroup's size, MAX_K the sort buffer's rows
 // (a power of two), WORDS the 64-bit words of a row of the NMS mask that the walk keeps in LDS.  Everything sits in an anonymous

@@ -938,3 +938,122 @@ def nms_bev_wide(boxes: torch.Tensor, counts: torch.Tensor, *, thresh: float, pr
                                 F.ptr(keep_count), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
     F.check(rc, f"lvq_nms_bev_wide ({g} groups of {n_max})")
     return keep, keep_count
+
+
+def heatmap_proposals(maps: torch.Tensor, *, first_channel: int, n_cls: int, point_class_mask: int, n_proposals: int, nms_kernel_size: int = 3,
+                      tag: Optional[str] = None):
+    """lvq_heatmap_proposals.  maps [B, c_total, H, W] fp32 with the heat-map logits in channels first_channel .. + n_cls - 1;
+    point_class_mask: bit c set = class c keeps every cell (no 3 x 3 suppression).  Returns (prop_flat [B, P] int32, prop_score [B, P],
+    query_heatmap_score [B, n_cls, P]): the P largest surviving heats in descending order, equal values towards the lower flat index."""
+    F.require_cuda(maps)
+    if maps.dim() != 4 or maps.dtype != torch.float32:
+        raise F.LvqError(f"heatmap_proposals: expected fp32 [B, C, H, W] maps, got {maps.dtype} {tuple(maps.shape)}")
+    b, c_total, h, w = maps.shape
+    dev, L, p = maps.device, F.lib(), int(n_proposals)
+    rows = max(p, 1)
+    flat = torch.empty((b, rows), dtype=torch.int32, device=dev)
+    score = torch.empty((b, rows), dtype=torch.float32, device=dev)
+    qhs = torch.empty((b, max(int(n_cls), 1), rows), dtype=torch.float32, device=dev)
+    nb = ctypes.c_size_t(0)
+    rc = L.lvq_heatmap_proposals_workspace_bytes(b, int(n_cls), h, w, ctypes.byref(nb))
+    ws = F.workspace(nb.value, dev, "transfusion_head") if rc == F.LVQ_OK else None   # a refused query: the call below names the reason
+    with region(tag, dev):
+        rc = L.lvq_heatmap_proposals(F.ptr(maps), b, c_total, h, w, int(first_channel), int(n_cls), int(point_class_mask), int(nms_kernel_size),
+                                     p, F.ptr(flat), F.ptr(score), F.ptr(qhs), F.ptr(ws), ws.numel() if ws is not None else 0,
+                                     F.stream_ptr(dev))
+    F.check(rc, f"lvq_heatmap_proposals (B={b}, {n_cls} classes, {h} x {w}, P={p}, NMS_KERNEL_SIZE={nms_kernel_size})")
+    return flat, score, qhs
+
+
+def pos_embed_learned(pos: torch.Tensor, w1: torch.Tensor, scale: torch.Tensor, shift: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor,
+                      tag: Optional[str] = None) -> torch.Tensor:
+    """lvq_pos_embed_learned.  pos [n, 2] fp32; w1 [d, 2], scale / shift [d] (BatchNorm1d and the first conv's bias folded), w2 [d_out, d],
+    b2 [d_out] -> [n, d_out] fp32."""
+    F.require_cuda(pos, w1, scale, shift, w2, b2)
+    if pos.dim() != 2 or pos.shape[1] != 2 or pos.dtype != torch.float32:
+        raise F.LvqError(f"pos_embed_learned: expected fp32 [n, 2] positions, got {pos.dtype} {tuple(pos.shape)}")
+    n, d, d_out = pos.shape[0], w1.shape[0], w2.shape[0]
+    if tuple(w1.shape) != (d, 2) or tuple(w2.shape) != (d_out, d) or any(tuple(t.shape) != (d,) for t in (scale, shift)) or \
+            tuple(b2.shape) != (d_out,):
+        raise F.LvqError(f"pos_embed_learned: w1 {tuple(w1.shape)}, w2 {tuple(w2.shape)} and the vectors do not agree on d, d_out")
+    out = torch.empty((n, d_out), dtype=torch.float32, device=pos.device)
+    with region(tag, pos.device):
+        rc = F.lib().lvq_pos_embed_learned(F.ptr(pos), n, d, d_out, F.ptr(w1), F.ptr(scale), F.ptr(shift), F.ptr(w2), F.ptr(b2), F.ptr(out),
+                                           F.stream_ptr(pos.device))
+    F.check(rc, f"lvq_pos_embed_learned (n={n}, d={d})")
+    return out
+
+
+def transfusion_queries(feat_hi: torch.Tensor, feat_lo: Optional[torch.Tensor], prop_flat: torch.Tensor, *, n_cls: int, y_size: int,
+                        class_w: torch.Tensor, class_b: torch.Tensor, pe, tag: Optional[str] = None):
+    """lvq_transfusion_queries.  feat_hi (+ feat_lo) [B, H, W, d] 16-bit planes, prop_flat [B, P] int32, class_w [d, n_cls], class_b [d],
+    pe = (w1, scale, shift, w2, b2) of pos_embed_learned.  Returns (query_feat [B, P, d], query_pos [B, P, 2], query_labels [B, P] int32,
+    query_pe [B, P, d])."""
+    F.require_cuda(feat_hi, feat_lo, prop_flat, class_w, class_b, *pe)
+    if feat_hi.dim() != 4 or feat_hi.element_size() != 2 or prop_flat.dtype != torch.int32 or prop_flat.dim() != 2 or \
+            prop_flat.shape[0] != feat_hi.shape[0]:
+        raise F.LvqError(f"transfusion_queries: expected 16-bit planes [B, H, W, d] and int32 prop_flat [B, P], got {tuple(feat_hi.shape)} and "
+                         f"{prop_flat.dtype} {tuple(prop_flat.shape)}")
+    b, h, w, d = feat_hi.shape
+    p, dev = prop_flat.shape[1], feat_hi.device
+    if tuple(class_w.shape) != (d, int(n_cls)) or tuple(class_b.shape) != (d,) or tuple(pe[3].shape) != (d, d):
+        raise F.LvqError(f"transfusion_queries: class_w {tuple(class_w.shape)}, class_b {tuple(class_b.shape)}, pe w2 {tuple(pe[3].shape)} with d = {d}")
+    feat = torch.empty((b, p, d), dtype=torch.float32, device=dev)
+    pos = torch.empty((b, p, 2), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, p), dtype=torch.int32, device=dev)
+    qpe = torch.empty((b, p, d), dtype=torch.float32, device=dev)
+    with region(tag, dev):
+        rc = F.lib().lvq_transfusion_queries(F.ptr(feat_hi), F.ptr(feat_lo), b, h, w, d, F.ptr(prop_flat), p, int(n_cls), int(y_size),
+                                             F.ptr(class_w), F.ptr(class_b), *[F.ptr(t) for t in pe], F.ptr(feat), F.ptr(pos), F.ptr(labels),
+                                             F.ptr(qpe), F.stream_ptr(dev))
+    F.check(rc, f"lvq_transfusion_queries (B={b}, {h} x {w}, d={d}, P={p})")
+    return feat, pos, labels, qpe
+
+
+def transfusion_add_pe(x: torch.Tensor, pe: torch.Tensor, split: bool) -> BF:
+    """lvq_transfusion_add_pe: x + pe (fp32, same shape) as a bf16 operand (hi, lo with `split`)."""
+    F.require_cuda(x, pe)
+    if x.shape != pe.shape or x.dtype != torch.float32 or pe.dtype != torch.float32:
+        raise F.LvqError(f"transfusion_add_pe: expected two fp32 tensors of one shape, got {tuple(x.shape)} and {tuple(pe.shape)}")
+    hi, lo = _bf_empty(x.shape, x.device, split)
+    F.check(F.lib().lvq_transfusion_add_pe(F.ptr(x), F.ptr(pe), x.numel(), F.ptr(hi), F.ptr(lo), F.stream_ptr(x.device)),
+            "lvq_transfusion_add_pe")
+    return hi, lo
+
+
+def transfusion_tail(x: torch.Tensor, query_pos: torch.Tensor, query_labels: torch.Tensor, prop_score: torch.Tensor, *, n_cls: int,
+                     has_vel: bool, ffn, norm, heads, eps: float, stride: int, voxel_xy, range_xy, limit_range, score_thresh: float,
+                     tag: Optional[str] = None):
+    """lvq_transfusion_tail.  x [B, P, 128] fp32 (after norm2); ffn = (w1 [F, 128], b1, w2 [128, F], b2), norm = (gamma, beta),
+    heads = (w1 [nb * 64, 128], scale, shift, w2 [c_total, 64], b2).  Returns (raw [B, c_total, P], boxes [B, P, 9 | 7], scores [B, P],
+    labels [B, P] int32 1-based, counts [B] int32): the kept rows in proposal order, zeros behind a count."""
+    F.require_cuda(x, query_pos, query_labels, prop_score, *ffn, *norm, *heads)
+    if x.dim() != 3 or x.dtype != torch.float32 or x.shape[2] != 128:
+        raise F.LvqError(f"transfusion_tail: expected fp32 [B, P, 128] rows, got {x.dtype} {tuple(x.shape)}")
+    b, p, _ = x.shape
+    f, dev, L = ffn[0].shape[0], x.device, F.lib()
+    c_box = 10 if has_vel else 8
+    nb, c_total, box_dim = (6 if has_vel else 5), c_box + int(n_cls), (9 if has_vel else 7)
+    want = [(tuple(query_pos.shape), (b, p, 2)), (tuple(query_labels.shape), (b, p)), (tuple(prop_score.shape), (b, p)),
+            (tuple(ffn[0].shape), (f, 128)), (tuple(ffn[1].shape), (f,)), (tuple(ffn[2].shape), (128, f)), (tuple(ffn[3].shape), (128,)),
+            (tuple(norm[0].shape), (128,)), (tuple(norm[1].shape), (128,)), (tuple(heads[0].shape), (nb * 64, 128)),
+            (tuple(heads[1].shape), (nb * 64,)), (tuple(heads[2].shape), (nb * 64,)), (tuple(heads[3].shape), (c_total, 64)),
+            (tuple(heads[4].shape), (c_total,))]
+    if any(g != w_ for g, w_ in want) or query_labels.dtype != torch.int32:
+        raise F.LvqError(f"transfusion_tail: operand shapes (got, expected) {[gw for gw in want if gw[0] != gw[1]]}, int32 labels")
+    raw = torch.empty((b, c_total, p), dtype=torch.float32, device=dev)
+    boxes = torch.empty((b, p, box_dim), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, p), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, p), dtype=torch.int32, device=dev)
+    counts = torch.empty((b,), dtype=torch.int32, device=dev)
+    nbytes = ctypes.c_size_t(0)
+    rc = L.lvq_transfusion_tail_workspace_bytes(b, p, box_dim, ctypes.byref(nbytes))
+    ws = F.workspace(nbytes.value, dev, "transfusion_tail") if rc == F.LVQ_OK else None   # a refused query: the call below names the reason
+    with region(tag, dev):
+        rc = L.lvq_transfusion_tail(F.ptr(x), F.ptr(query_pos), F.ptr(query_labels), F.ptr(prop_score), b, p, f, int(n_cls), int(has_vel),
+                                    *[F.ptr(t) for t in ffn], *[F.ptr(t) for t in norm], float(eps), *[F.ptr(t) for t in heads], int(stride),
+                                    F.f32x(voxel_xy), F.f32x(range_xy), F.f32x(limit_range), float(score_thresh), F.ptr(raw), F.ptr(boxes),
+                                    F.ptr(scores), F.ptr(labels), F.ptr(counts), F.ptr(ws), ws.numel() if ws is not None else 0,
+                                    F.stream_ptr(dev))
+    F.check(rc, f"lvq_transfusion_tail (B={b}, P={p}, FFN={f}, {n_cls} classes)")
+    return raw, boxes, scores, labels, counts
