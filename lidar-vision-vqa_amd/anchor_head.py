@@ -40,6 +40,9 @@ post_processing, MULTI_CLASSES_NMS False, NMS_TYPE nms_gpu:
 Supported: ResidualCoder with code_size 7 and no encode_angle_by_sincos; one anchor size and one bottom height per class, the same number
 of rotations for every class; input channels <= 512; NMS_PRE_MAXSIZE <= 4096.  Anything else raises LvqError naming the limit, before any
 launch.  `precision`: "bf16x3" (default) or "bf16", as on the other heads.
+
+Shared with the other heads through head_common.py: the forward preamble (guard), the end of post_processing (collect_kept: the collect,
+the copy, the slices) and the torch route's NMS (class_agnostic_nms_torch); the fused conv is dense_head._Fused with a 1 x 1 kernel.
 """
 from __future__ import annotations
 
@@ -51,11 +54,11 @@ import torch
 import torch.nn as nn
 
 from . import _ffi as F
-from . import autograd_route as AG
 from . import ops
 from . import sparse_head as SH
-from .backbone2d import DEFAULT_MODE, MODES, to_planes
-from .dense_head import _Fused, _get
+from .backbone2d import to_planes
+from .dense_head import _Fused
+from .head_common import _get, cached_plan, class_agnostic_nms_torch, collect_kept, guard
 
 MAX_PRE = 4096                 # lvq_anchor_select's sort rows and lvq_nms_bev_wide's 64 mask words
 CODE_SIZE = 7
@@ -137,34 +140,27 @@ class ResidualCoder:
         raise F.LvqError("ResidualCoder.encode_torch: training targets are out of scope (inference-only kernels)")
 
 
-class _Fused1(_Fused):
+def _fused_1x1(convs: List[nn.Conv2d], c_in: int, c_out: int) -> _Fused:
     """dense_head._Fused with a 1 x 1 kernel: the head's convs as one conv C -> c_out, the biases as the shift."""
+    def weight():
+        w = convs[0].weight.new_zeros((c_out, c_in, 1, 1), dtype=torch.float32)
+        row = 0
+        for m in convs:
+            w[row:row + m.out_channels] = m.weight.detach().float()
+            row += m.out_channels
+        return w
 
-    def __init__(self, convs: List[nn.Conv2d], c_in: int, c_out: int):
-        def weight():
-            w = convs[0].weight.new_zeros((c_out, c_in, 1, 1), dtype=torch.float32)
-            row = 0
-            for m in convs:
-                w[row:row + m.out_channels] = m.weight.detach().float()
-                row += m.out_channels
-            return w
+    def affine():
+        shift = convs[0].weight.new_zeros((c_out,), dtype=torch.float32)
+        row = 0
+        for m in convs:
+            shift[row:row + m.out_channels] = m.bias.detach().float()
+            row += m.out_channels
+        return torch.ones_like(shift), shift
 
-        def affine():
-            shift = convs[0].weight.new_zeros((c_out,), dtype=torch.float32)
-            row = 0
-            for m in convs:
-                shift[row:row + m.out_channels] = m.bias.detach().float()
-                row += m.out_channels
-            return torch.ones_like(shift), shift
-
-        super().__init__(convs, c_in, c_out, False, weight, affine, [m.weight for m in convs] + [m.bias for m in convs])
-        self.kernel, self.stride, self.padding = 1, 1, 0
-
-    def packed(self, split: bool):
-        def build():
-            hi, lo = ops.conv2d_pack_weights(self._weight().contiguous(), self.c_out, self.c_in, 1, False, split)
-            return hi.view(torch.int16), None if lo is None else lo.view(torch.int16)
-        return F.derived(self._cache, ("w", split), self._params, build)
+    fused = _Fused(convs, c_in, c_out, False, weight, affine, [m.weight for m in convs] + [m.bias for m in convs])
+    fused.kernel, fused.stride, fused.padding = 1, 1, 0
+    return fused
 
 
 class AnchorHeadSingle(nn.Module):
@@ -243,9 +239,9 @@ class AnchorHeadSingle(nn.Module):
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def _plan(self):
-        plan = self.__dict__.get("_plan_cache")
-        if plan is not None:
-            return plan
+        return cached_plan(self, self._build_plan)
+
+    def _build_plan(self):
         c_in = self.conv_cls.in_channels
         if c_in > 512:
             raise F.LvqError(f"AnchorHeadSingle: {c_in} input channels; lvq_conv2d takes at most 512")
@@ -257,9 +253,7 @@ class AnchorHeadSingle(nn.Module):
         c_out = (o + 63) // 64 * 64
         if c_out > 512:
             raise F.LvqError(f"AnchorHeadSingle: {o} output channels in all; one lvq_conv2d launch writes at most 512")
-        plan = dict(fused=_Fused1(convs, c_in, c_out), c_out=c_out, cls=offs[0], box=offs[1], dir=offs[2] if len(convs) == 3 else -1)
-        self.__dict__["_plan_cache"] = plan
-        return plan
+        return dict(fused=_fused_1x1(convs, c_in, c_out), c_out=c_out, cls=offs[0], box=offs[1], dir=offs[2] if len(convs) == 3 else -1)
 
     def flat_anchors(self):
         """The anchors as generate_predicted_boxes flattens them: [H * W * A, 7] in the order (y, x, class, rotation); cached per version."""
@@ -286,15 +280,7 @@ class AnchorHeadSingle(nn.Module):
 
     def forward(self, data_dict):
         x = data_dict["spatial_features_2d"]
-        if AG.wanted(self, x):
-            raise F.LvqError("AnchorHeadSingle: inference-only kernels (no target assignment, no losses); call it in eval() mode under "
-                             "torch.no_grad()")
-        mode = self.precision or DEFAULT_MODE
-        if mode not in MODES:
-            raise F.LvqError(f"AnchorHeadSingle runs in {MODES}, not {mode!r}")
-        if x.dim() != 4:
-            raise F.LvqError(f"AnchorHeadSingle: expected [B, C, H, W], got {tuple(x.shape)}")
-        F.require_cuda(x.contiguous(), *self.parameters(), *self.anchors)
+        split = guard(self, "no target assignment, no losses", x, extra_cuda=self.anchors)
         plan = self._plan()                            # refusals come before any launch
         a0 = self.anchors[0]
         if tuple(x.shape[2:]) != tuple(a0.shape[1:3]):
@@ -303,7 +289,7 @@ class AnchorHeadSingle(nn.Module):
         batch_size = int(data_dict["batch_size"])
         if batch_size != x.shape[0]:
             raise F.LvqError(f"AnchorHeadSingle: batch_size = {batch_size}, spatial_features_2d holds {x.shape[0]} scenes")
-        maps = self._maps(x.float().contiguous(), mode == "bf16x3")
+        maps = self._maps(x.float().contiguous(), split)
         ret, A = self.forward_ret_dict, self.num_anchors_per_location
         ret["cls_preds"] = maps[:, plan["cls"]:plan["cls"] + A * self.num_class].permute(0, 2, 3, 1)
         ret["box_preds"] = maps[:, plan["box"]:plan["box"] + A * CODE_SIZE].permute(0, 2, 3, 1)
@@ -377,13 +363,12 @@ def post_processing(batch_dict, post_process_cfg, num_class):
     keep, keep_count = ops.nms_bev_wide(sel_boxes, sel_count, thresh=post["nms_thresh"], pre_max=post["pre"], post_max=post["post"],
                                         tag="anchor_nms")
     b, k = sel_scores.shape
-    out_b, out_s, out_l, _ = ops.center_collect(sel_boxes.view(b, 1, k, CODE_SIZE), sel_scores.view(b, 1, k), sel_labels.view(b, 1, k), keep,
-                                                keep_count, tag="anchor_collect")
+    raw = None
     if post["raw"]:                                    # max_k of the raw logits at the selected anchors
         anchor = sel_index.gather(1, keep.clamp(min=0).long()).clamp(min=0).long()
-        out_s = cls.gather(1, anchor.unsqueeze(-1).expand(-1, -1, cls.shape[-1])).max(dim=-1)[0]
-    totals = keep_count.cpu().tolist()                 # THE device-to-host copy
-    return [dict(pred_boxes=out_b[s, :n], pred_scores=out_s[s, :n], pred_labels=out_l[s, :n]) for s, n in enumerate(totals)], {}
+        raw = cls.gather(1, anchor.unsqueeze(-1).expand(-1, -1, cls.shape[-1])).max(dim=-1)[0]
+    return collect_kept(sel_boxes.view(b, 1, k, CODE_SIZE), sel_scores.view(b, 1, k), sel_labels.view(b, 1, k), keep, keep_count,
+                        "anchor_collect", pred_scores=raw), {}      # holds THE device-to-host copy
 
 
 def _torch_post(cls, box, normalized, post):
@@ -398,18 +383,7 @@ def _torch_post(cls, box, normalized, post):
         if post["thresh"] is not None:
             scores_mask = box_scores >= post["thresh"]
             box_scores, boxes_m = box_scores[scores_mask], box_preds[scores_mask]
-        selected = torch.zeros((0,), dtype=torch.int64, device=box.device)
-        if box_scores.shape[0] > 0:
-            box_scores_nms, indices = torch.topk(box_scores, k=min(post["pre"], box_scores.shape[0]))
-            order = box_scores_nms.sort(0, descending=True)[1]              # nms_gpu's own sort
-            nms_boxes = boxes_m[indices][order][:, :7].float().contiguous()
-            over = (ops.boxes_iou_bev(nms_boxes, nms_boxes) > post["nms_thresh"]).cpu().numpy()
-            kept, gone = [], over[0] & False
-            for i in range(over.shape[0]):
-                if not gone[i]:
-                    kept.append(i)
-                    gone[i + 1:] |= over[i, i + 1:]
-            selected = indices[order[torch.tensor(kept[:post["post"]], dtype=torch.int64, device=box.device)]]
+        selected = class_agnostic_nms_torch(boxes_m, box_scores, post)
         if post["thresh"] is not None:
             selected = scores_mask.nonzero().view(-1)[selected]
         final_scores = torch.max(src_cls_preds, dim=-1)[0][selected] if post["raw"] else cls_preds[selected]

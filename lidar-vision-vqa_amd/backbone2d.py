@@ -25,11 +25,9 @@ import torch
 import torch.nn as nn
 
 from . import _ffi as F
-from . import autograd_route as AG
 from . import ops
+from .head_common import DEFAULT_MODE, MODES, _get, cached_plan, guard  # noqa: F401  (the precision names are re-exported)
 
-MODES = ("bf16x3", "bf16")
-DEFAULT_MODE = "bf16x3"
 FAMILY = "c_in 1 .. 512, c_out a multiple of 64 in 64 .. 512; kernel 3 at stride 1 / 2, or kernel = stride in 1, 2, 4"
 _lib = F.lib
 
@@ -182,31 +180,12 @@ def _deblock(c_in, c_out, stride, transposed: bool) -> nn.Sequential:
     return nn.Sequential(conv, nn.BatchNorm2d(c_out, eps=1e-3, momentum=0.01), nn.ReLU())
 
 
-def _get(cfg, key, default=None):
-    v = cfg.get(key, default) if hasattr(cfg, "get") else getattr(cfg, key, default)
-    return default if v is None else v
-
-
 class _Backbone2d(nn.Module):
     def _plan(self):
-        plan = self.__dict__.get("_plan_cache")
-        if plan is None:
-            plan = dict(blocks=[_layers(b) for b in self.blocks], deblocks=[_layers(d) for d in self.deblocks])
-            self.__dict__["_plan_cache"] = plan
-        return plan
+        return cached_plan(self, lambda: dict(blocks=[_layers(b) for b in self.blocks], deblocks=[_layers(d) for d in self.deblocks]))
 
     def _guard(self, *tensors) -> bool:
-        name = type(self).__name__
-        if AG.wanted(self, *tensors):
-            raise F.LvqError(f"{name}: inference-only kernels (BatchNorm folded); call it in eval() mode under torch.no_grad()")
-        mode = self.precision or DEFAULT_MODE
-        if mode not in MODES:
-            raise F.LvqError(f"{name} runs in {MODES}, not {mode!r}")
-        for t in tensors:
-            if t.dim() != 4:
-                raise F.LvqError(f"{name}: expected [B, C, H, W], got {tuple(t.shape)}")
-        F.require_cuda(*[t.contiguous() for t in tensors], *self.parameters())
-        return mode == "bf16x3"
+        return guard(self, "BatchNorm folded", *tensors)
 
     @staticmethod
     def _chain(layers, x: Planes, split: bool, **last) -> Planes:

@@ -3,8 +3,8 @@
 //   k_center_decode    centernet_utils.py:155-241.  One workgroup of 1024 threads per (scene, task): a 4 x 8-bit radix select of the K-th
 //                      largest fp32 score over n_cls * H * W, a bitonic sort of the K winners in LDS, the box arithmetic, the masks and
 //                      an order-keeping compaction.  Nothing is handed between workgroups.
-//   k_voxel_decode     centernet_utils.py:243-354 (VoxelNeXtHead): the same selection, sort, masks and compaction (select_sort, decode_box, box_stays,
-//                      compact_store are shared, not copied) over the ROWS of a sparse tensor: the candidates of a scene are the rows
+//   k_voxel_decode     centernet_utils.py:243-354 (VoxelNeXtHead): the same selection, sort, masks and compaction (select_sort and
+//                      decode_winners are shared, not copied) over the ROWS of a sparse tensor: the candidates of a scene are the rows
 //                      whose batch index is the scene's, in stored order and not necessarily contiguous; y and x come from the rows'
 //                      own indices.  One deliberate difference from the reference: when a scene has fewer than K rows, _topk_1d still
 //                      computes class = ind // K on an [n_cls, n_b] matrix, which gives wrong classes, and when n_cls * n_b < K its
@@ -29,8 +29,12 @@
 // boxes give an area that rounds to zero, identical boxes the full area, and nothing has to be made robust by moving a corner.
 // IoU = area / max(sa + sb - area, 1e-8), as iou3d_nms_kernel.cu:217-234 divides.
 //
-// The selection (key_of, select_sort), the rectangles (Rect, rect_iou) and k_nms_mask / k_nms_walk live in head_common.h, which
-// anchor_head.hip shares; this file instantiates them for 1024 threads, 1024 sort rows and 16 mask words.
+// The selection (key_of, select_sort), the rectangles (Rect, rect_iou), k_nms_mask / k_nms_walk, the grid's geometry (CenterGeom), the
+// range-and-threshold mask (box_stays) and the compaction (compact_store) live in head_common.h, which anchor_head.hip and
+// transfusion_head.hip share; this file instantiates them for 1024 threads, 1024 sort rows and 16 mask words.  What the two decode kernels
+// share beyond that is here: the box arithmetic (decode_box), the tail "winner tid of the sort buffer: decode, mask, label, compact"
+// (decode_winners, with the index-to-cell mapping as a callable) and, on the host, center_tables, which builds CenterTasks and CenterGeom
+// from the ABI's arrays for both entry points.
 //
 // Every store below is an ordinary vector store from C++; LDS counters use ds atomics.
 #include "head_common.h"
@@ -49,9 +53,6 @@ struct CenterTasks {                   // by value in the kernel arguments
     int map_off[MAX_TASKS];
     int cls_map[MAX_CLASSES];
 };
-struct CenterGeom {
-    float stride, vx, vy, rx, ry, lim[6], thresh;
-};
 
 // the box of a candidate at cell (x, y); ch(c) reads channel c at the candidate (centernet_utils.py:184-212 / 310-319)
 template <class Ch>
@@ -65,35 +66,28 @@ __device__ __forceinline__ void decode_box(Ch ch, int x, int y, const int *off, 
     if (box_dim == 9) { bx[7] = ch(off[4]); bx[8] = ch(off[4] + 1); }
 }
 
-// masks of centernet_utils.py:214-221 / 332-336
-__device__ __forceinline__ bool box_stays(const float *bx, float sc, const CenterGeom &gm) {
-    return bx[0] >= gm.lim[0] && bx[1] >= gm.lim[1] && bx[2] >= gm.lim[2] && bx[0] <= gm.lim[3] && bx[1] <= gm.lim[4] && bx[2] <= gm.lim[5] &&
-           (gm.thresh < 0.f || sc > gm.thresh);
-}
-
-// order-keeping compaction of the kept candidates of group g (thread tid holds candidate tid) into rows g * K ..; rows behind the count
-// are zeroed, counts[g] is written.  Every thread of the workgroup calls it.
-__device__ void compact_store(uint32_t *wcnt, bool keep, const float *bx, float sc, int label, int g, int K, int box_dim,
-                              float *__restrict__ boxes, float *__restrict__ scores, int32_t *__restrict__ labels, int32_t *__restrict__ counts) {
-    const int tid = threadIdx.x;
-    const uint64_t bal = __ballot(keep);
-    const int lane = tid & 63, wave = tid >> 6;
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-    for (int q = 0; q < DEC_THREADS / 64; ++q) { const uint32_t c = wcnt[q]; total += c; if (q < wave) rank += c; }
-    const int64_t row0 = (int64_t)g * K;
-    if (keep) {
-        for (int d = 0; d < box_dim; ++d) boxes[(row0 + rank) * box_dim + d] = bx[d];
-        scores[row0 + rank] = sc;
-        labels[row0 + rank] = label;
+// Thread tid < n_win holds winner tid of the sort buffer: its box, the masks, its label, then the compaction of the group's winners
+// (centernet_utils.py:184-221 / 310-336).  locate(idx, cls, x, y) splits the flat index into the class and the cell and returns the
+// reader of a channel at that candidate.  Every thread of the workgroup calls it.
+template <class Locate>
+__device__ __forceinline__ void decode_winners(SelectLds<DEC_THREADS, MAX_K> &s, int n_win, Locate locate, const CenterTasks &tk, int t,
+                                               const CenterGeom &gm, int g, int K, int box_dim, float *__restrict__ boxes,
+                                               float *__restrict__ scores, int32_t *__restrict__ labels, int32_t *__restrict__ counts) {
+    bool keep = false;
+    float bx[9];
+    float sc = 0.f;
+    int label = 0;
+    if ((int)threadIdx.x < n_win) {
+        const uint64_t e = s.buf[threadIdx.x];
+        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
+        sc = score_of((uint32_t)(e >> 32));
+        int cls, x, y;
+        const auto ch = locate(idx, cls, x, y);
+        decode_box(ch, x, y, tk.off[t], gm, box_dim, bx);
+        keep = box_stays<true>(bx, sc, gm);
+        label = tk.cls_map[tk.map_off[t] + cls];
     }
-    if (tid >= (int)total && tid < K) {                          // rows behind the count hold zeros, not what an earlier call left
-        for (int d = 0; d < box_dim; ++d) boxes[(row0 + tid) * box_dim + d] = 0.f;
-        scores[row0 + tid] = 0.f;
-        labels[row0 + tid] = 0;
-    }
-    if (tid == 0) counts[g] = (int32_t)total;
+    compact_store<DEC_THREADS>(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
 }
 
 __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__restrict__ maps, int c_total, int h, int w, int n_tasks,
@@ -102,28 +96,18 @@ __global__ __launch_bounds__(DEC_THREADS) void k_center_decode(const float *__re
                                                                 int32_t *__restrict__ labels, int32_t *__restrict__ counts,
                                                                 uint32_t *__restrict__ keys_ws, int64_t keys_pitch) {
     __shared__ SelectLds<DEC_THREADS, MAX_K> s;
-    const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks, tid = threadIdx.x;
+    const int g = blockIdx.x, b = g / n_tasks, t = g - b * n_tasks;
     const int64_t hw = (int64_t)h * w;
     const int n = (int)(tk.n_cls[t] * hw);
     const float *scene = maps + (int64_t)b * c_total * hw;
     const float *hm = scene + (int64_t)tk.off[t][5] * hw;
     select_sort<DEC_THREADS, MAX_K, false>(s, [hm](int i) { return key_of(1.0f / (1.0f + expf(-hm[i]))); }, keys_ws + (int64_t)g * keys_pitch, n, K);
-    // ---- decode, mask, compact (centernet_utils.py:184-221)
-    bool keep = false;
-    float bx[9];
-    float sc = 0.f;
-    int label = 0;
-    if (tid < K) {
-        const uint64_t e = s.buf[tid];
-        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
-        sc = score_of((uint32_t)(e >> 32));
-        const int cls = (int)(idx / (uint32_t)hw), pix = (int)(idx - (uint32_t)cls * (uint32_t)hw);
-        const int y = pix / w, x = pix - y * w;
-        decode_box([&](int c) { return scene[(int64_t)c * hw + pix]; }, x, y, tk.off[t], gm, box_dim, bx);
-        keep = box_stays(bx, sc, gm);
-        label = tk.cls_map[tk.map_off[t] + cls];
-    }
-    compact_store(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
+    decode_winners(s, K, [&](uint32_t idx, int &cls, int &x, int &y) {
+        cls = (int)(idx / (uint32_t)hw);
+        const int pix = (int)(idx - (uint32_t)cls * (uint32_t)hw);
+        y = pix / w; x = pix - y * w;
+        return [=](int c) { return scene[(int64_t)c * hw + pix]; };
+    }, tk, t, gm, g, K, box_dim, boxes, scores, labels, counts);
 }
 
 // centernet_utils.py:243-354 over rows: the candidates of scene b are the rows with indices[:, 0] == b, flat index = class * n + stored row,
@@ -153,21 +137,12 @@ __global__ __launch_bounds__(DEC_THREADS) void k_voxel_decode(const float *__res
             const int row = i % n_rows;
             return indices[3 * (int64_t)row] == b ? key_of(1.0f / (1.0f + expf(-hm[i]))) : 0u;
         }, keys_ws + (int64_t)g * keys_pitch, n_cls * n_rows, k_eff);
-    bool keep = false;
-    float bx[9];
-    float sc = 0.f;
-    int label = 0;
-    if (tid < k_eff) {
-        const uint64_t e = s.buf[tid];
-        const uint32_t idx = 0xffffffffu - (uint32_t)(e & 0xffffffffu);
-        sc = score_of((uint32_t)(e >> 32));
-        const int cls = (int)(idx / (uint32_t)n_rows), row = (int)(idx - (uint32_t)cls * (uint32_t)n_rows);
-        const int y = indices[3 * (int64_t)row + 1], x = indices[3 * (int64_t)row + 2];
-        decode_box([&](int c) { return head[(int64_t)c * n_rows + row]; }, x, y, tk.off[t], gm, box_dim, bx);
-        keep = box_stays(bx, sc, gm);
-        label = tk.cls_map[tk.map_off[t] + cls];
-    }
-    compact_store(s.wcnt, keep, bx, sc, label, g, K, box_dim, boxes, scores, labels, counts);
+    decode_winners(s, k_eff, [&](uint32_t idx, int &cls, int &x, int &y) {
+        cls = (int)(idx / (uint32_t)n_rows);
+        const int row = (int)(idx - (uint32_t)cls * (uint32_t)n_rows);
+        y = indices[3 * (int64_t)row + 1]; x = indices[3 * (int64_t)row + 2];
+        return [=](int c) { return head[(int64_t)c * n_rows + row]; };
+    }, tk, t, gm, g, K, box_dim, boxes, scores, labels, counts);
 }
 
 __global__ __launch_bounds__(256) void k_boxes_iou_bev(const float *__restrict__ a, int n, const float *__restrict__ bb, int m,
@@ -205,6 +180,38 @@ __global__ __launch_bounds__(256) void k_center_collect(const float *__restrict_
     }
 }
 
+// lvq_center_decode / lvq_voxel_decode: the ABI's host tables as CenterTasks and CenterGeom, with the refusals both entry points share, in
+// their order.  cells >= 0: k may not exceed n_cls * cells in any task (the dense map's H * W; torch.topk raises there).
+int center_tables(int n_tasks, const int32_t *task_channels, const int32_t *task_n_cls, const int32_t *class_map, int c_total, int k,
+                  int box_dim, int stride, const float *voxel_xy, const float *range_xy, const float *limit_range, float score_thresh,
+                  int64_t cells, CenterTasks &tk, CenterGeom &gm, int &max_cls) {
+    if (n_tasks > MAX_TASKS) return LVQ_EUNSUPPORTED;
+    tk = {};
+    const int width[6] = {2, 1, 3, 2, 2, 0};
+    int total_cls = 0;
+    max_cls = 0;
+    for (int t = 0; t < n_tasks; ++t) {
+        const int nc = task_n_cls[t];
+        if (nc <= 0) return LVQ_EINVAL;
+        if (total_cls + nc > MAX_CLASSES) return LVQ_EUNSUPPORTED;
+        if (cells >= 0 && (int64_t)k > (int64_t)nc * cells) return LVQ_EINVAL;
+        for (int f = 0; f < 6; ++f) {
+            const int c = task_channels[t * 6 + f], wd = f == 5 ? nc : width[f];
+            if (f == 4 ? (box_dim == 9) != (c >= 0) : c < 0) return LVQ_EINVAL; // vel in every task of a 9-wide box, in none of a 7-wide one
+            if (c >= 0 && c + wd > c_total) return LVQ_EINVAL;
+            tk.off[t][f] = c;
+        }
+        tk.n_cls[t] = nc;
+        tk.map_off[t] = total_cls;
+        for (int c = 0; c < nc; ++c) tk.cls_map[total_cls + c] = class_map[total_cls + c];
+        total_cls += nc;
+        max_cls = nc > max_cls ? nc : max_cls;
+    }
+    if (k > MAX_K) return LVQ_EUNSUPPORTED;
+    gm = center_geom(stride, voxel_xy, range_xy, limit_range, score_thresh);
+    return LVQ_OK;
+}
+
 }  // namespace
 
 extern "C" int lvq_center_decode_workspace_bytes(int batch, int n_tasks, int max_cls, int h, int w, size_t *bytes) {
@@ -224,36 +231,16 @@ extern "C" int lvq_center_decode(const float *maps, int batch, int c_total, int 
     if (!maps || !task_channels || !task_n_cls || !class_map || !voxel_xy || !range_xy || !limit_range || !boxes || !scores || !labels ||
         !counts || batch <= 0 || c_total <= 0 || h <= 0 || w <= 0 || n_tasks <= 0 || k <= 0 || stride <= 0 || (box_dim != 7 && box_dim != 9))
         return LVQ_EINVAL;
-    if (n_tasks > MAX_TASKS) return LVQ_EUNSUPPORTED;
-    CenterTasks tk = {};
-    const int width[6] = {2, 1, 3, 2, 2, 0};
-    int max_cls = 0, total_cls = 0;
-    for (int t = 0; t < n_tasks; ++t) {
-        const int nc = task_n_cls[t];
-        if (nc <= 0) return LVQ_EINVAL;
-        if (total_cls + nc > MAX_CLASSES) return LVQ_EUNSUPPORTED;
-        if ((int64_t)k > (int64_t)nc * h * w) return LVQ_EINVAL;                 // torch.topk raises there
-        for (int f = 0; f < 6; ++f) {
-            const int c = task_channels[t * 6 + f], wd = f == 5 ? nc : width[f];
-            if (f == 4 ? (box_dim == 9) != (c >= 0) : c < 0) return LVQ_EINVAL; // vel in every task of a 9-wide box, in none of a 7-wide one
-            if (c >= 0 && c + wd > c_total) return LVQ_EINVAL;
-            tk.off[t][f] = c;
-        }
-        tk.n_cls[t] = nc;
-        tk.map_off[t] = total_cls;
-        for (int c = 0; c < nc; ++c) tk.cls_map[total_cls + c] = class_map[total_cls + c];
-        total_cls += nc;
-        max_cls = nc > max_cls ? nc : max_cls;
-    }
-    if (k > MAX_K) return LVQ_EUNSUPPORTED;
+    CenterTasks tk;
+    CenterGeom gm;
+    int max_cls = 0;
+    int rc = center_tables(n_tasks, task_channels, task_n_cls, class_map, c_total, k, box_dim, stride, voxel_xy, range_xy, limit_range,
+                           score_thresh, (int64_t)h * w, tk, gm, max_cls);
+    if (rc != LVQ_OK) return rc;
     size_t need = 0;
-    const int rc = lvq_center_decode_workspace_bytes(batch, n_tasks, max_cls, h, w, &need);
+    rc = lvq_center_decode_workspace_bytes(batch, n_tasks, max_cls, h, w, &need);
     if (rc != LVQ_OK) return rc;
     if (!ws || ws_bytes < need) return LVQ_EWORKSPACE;
-    CenterGeom gm;
-    gm.stride = (float)stride; gm.vx = voxel_xy[0]; gm.vy = voxel_xy[1]; gm.rx = range_xy[0]; gm.ry = range_xy[1];
-    for (int i = 0; i < 6; ++i) gm.lim[i] = limit_range[i];
-    gm.thresh = score_thresh;
     const int64_t pitch = (int64_t)(lvq_align((size_t)max_cls * h * w * 4, 256) / 4);
     LvqArena arena(ws, ws_bytes);
     uint32_t *keys = arena.take<uint32_t>((size_t)batch * n_tasks * pitch);
@@ -281,35 +268,16 @@ extern "C" int lvq_voxel_decode(const float *head, const int32_t *indices, int64
         batch <= 0 || c_total <= 0 || n_rows < 0 || n_tasks <= 0 || k <= 0 || stride <= 0 || (box_dim != 7 && box_dim != 9) ||
         (n_rows > 0 && (!head || !indices)))
         return LVQ_EINVAL;
-    if (n_tasks > MAX_TASKS) return LVQ_EUNSUPPORTED;
-    CenterTasks tk = {};
-    const int width[6] = {2, 1, 3, 2, 2, 0};
-    int max_cls = 0, total_cls = 0;
-    for (int t = 0; t < n_tasks; ++t) {
-        const int nc = task_n_cls[t];
-        if (nc <= 0) return LVQ_EINVAL;
-        if (total_cls + nc > MAX_CLASSES) return LVQ_EUNSUPPORTED;
-        for (int f = 0; f < 6; ++f) {
-            const int c = task_channels[t * 6 + f], wd = f == 5 ? nc : width[f];
-            if (f == 4 ? (box_dim == 9) != (c >= 0) : c < 0) return LVQ_EINVAL; // vel in every task of a 9-wide box, in none of a 7-wide one
-            if (c >= 0 && c + wd > c_total) return LVQ_EINVAL;
-            tk.off[t][f] = c;
-        }
-        tk.n_cls[t] = nc;
-        tk.map_off[t] = total_cls;
-        for (int c = 0; c < nc; ++c) tk.cls_map[total_cls + c] = class_map[total_cls + c];
-        total_cls += nc;
-        max_cls = nc > max_cls ? nc : max_cls;
-    }
-    if (k > MAX_K) return LVQ_EUNSUPPORTED;
+    CenterTasks tk;
+    CenterGeom gm;
+    int max_cls = 0;
+    int rc = center_tables(n_tasks, task_channels, task_n_cls, class_map, c_total, k, box_dim, stride, voxel_xy, range_xy, limit_range,
+                           score_thresh, -1, tk, gm, max_cls);
+    if (rc != LVQ_OK) return rc;
     size_t need = 0;
-    const int rc = lvq_voxel_decode_workspace_bytes(batch, n_tasks, max_cls, n_rows, &need);
+    rc = lvq_voxel_decode_workspace_bytes(batch, n_tasks, max_cls, n_rows, &need);
     if (rc != LVQ_OK) return rc;
     if (!ws || ws_bytes < need) return LVQ_EWORKSPACE;
-    CenterGeom gm;
-    gm.stride = (float)stride; gm.vx = voxel_xy[0]; gm.vy = voxel_xy[1]; gm.rx = range_xy[0]; gm.ry = range_xy[1];
-    for (int i = 0; i < 6; ++i) gm.lim[i] = limit_range[i];
-    gm.thresh = score_thresh;
     const int64_t pitch = (int64_t)(lvq_align((size_t)max_cls * n_rows * 4 + 4, 256) / 4);
     LvqArena arena(ws, ws_bytes);
     uint32_t *keys = arena.take<uint32_t>((size_t)batch * n_tasks * pitch);

@@ -1,8 +1,9 @@
 // csrc/head_common.h -- what the dense heads' post-processing kernels share (center_head.hip, anchor_head.hip, transfusion_head.hip): the order of fp32
-// scores as unsigned keys, the radix select + bitonic sort of the K best candidates, rotated rectangles and their IoU, and the two
-// kernels of the rotated BEV NMS.  Sizes are template parameters: THREADS is the workgroup's size, MAX_K the sort buffer's rows
-// (a power of two), WORDS the 64-bit words of a row of the NMS mask that the walk keeps in LDS.  Everything sits in an anonymous
-// namespace: each translation unit instantiates what it launches.
+// scores as unsigned keys, the radix select + bitonic sort of the K best candidates, rotated rectangles and their IoU, the two
+// kernels of the rotated BEV NMS, and for the heads that decode boxes on a grid (center_head.hip, transfusion_head.hip) the grid's
+// geometry (CenterGeom), the range-and-threshold mask (box_stays) and the order-keeping compaction (compact_store).  Sizes are template
+// parameters: THREADS is the workgroup's size, MAX_K the sort buffer's rows (a power of two), WORDS the 64-bit words of a row of the NMS
+// mask that the walk keeps in LDS.  Everything sits in an anonymous namespace: each translation unit instantiates what it launches.
 //
 // Every store below is an ordinary vector store from C++; LDS counters use ds atomics.
 #pragma once
@@ -338,6 +339,56 @@ __global__ __launch_bounds__(64) void k_nms_walk(const uint64_t *__restrict__ ma
     cnt = min(cnt, post_max);
     for (int e = cnt + lane; e < post_max; e += 64) out[e] = -1;
     if (lane == 0) keep_count[g] = cnt;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// decoded boxes: the geometry of the grid, the range-and-threshold mask, the order-keeping compaction
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct CenterGeom {                    // by value in the kernel arguments
+    float stride, vx, vy, rx, ry, lim[6], thresh;
+};
+
+inline CenterGeom center_geom(int stride, const float *voxel_xy, const float *range_xy, const float *limit_range, float score_thresh) {
+    CenterGeom gm;
+    gm.stride = (float)stride; gm.vx = voxel_xy[0]; gm.vy = voxel_xy[1]; gm.rx = range_xy[0]; gm.ry = range_xy[1];
+    for (int i = 0; i < 6; ++i) gm.lim[i] = limit_range[i];
+    gm.thresh = score_thresh;
+    return gm;
+}
+
+// the centre inside the limit range and the score above the threshold (centernet_utils.py:214-221 / 332-336, transfusion_head.py:433-451).
+// THRESH_OPTIONAL: a negative threshold stands for "none" and keeps every score (the centre heads' SCORE_THRESH None); without it the
+// threshold is applied whatever its sign (TransFusionHead).
+template <bool THRESH_OPTIONAL>
+__device__ __forceinline__ bool box_stays(const float *bx, float sc, const CenterGeom &gm) {
+    return bx[0] >= gm.lim[0] && bx[1] >= gm.lim[1] && bx[2] >= gm.lim[2] && bx[0] <= gm.lim[3] && bx[1] <= gm.lim[4] && bx[2] <= gm.lim[5] &&
+           ((THRESH_OPTIONAL && gm.thresh < 0.f) || sc > gm.thresh);
+}
+
+// order-keeping compaction of the kept candidates of group g (thread tid holds candidate tid) into rows g * K ..; rows behind the count
+// are zeroed, counts[g] is written.  wcnt: THREADS / 64 LDS words.  Every thread of the workgroup (THREADS of them) calls it.
+template <int THREADS>
+__device__ void compact_store(uint32_t *wcnt, bool keep, const float *bx, float sc, int label, int g, int K, int box_dim,
+                              float *__restrict__ boxes, float *__restrict__ scores, int32_t *__restrict__ labels, int32_t *__restrict__ counts) {
+    const int tid = threadIdx.x;
+    const uint64_t bal = __ballot(keep);
+    const int lane = tid & 63, wave = tid >> 6;
+    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), total = 0;
+    for (int q = 0; q < THREADS / 64; ++q) { const uint32_t c = wcnt[q]; total += c; if (q < wave) rank += c; }
+    const int64_t row0 = (int64_t)g * K;
+    if (keep) {
+        for (int d = 0; d < box_dim; ++d) boxes[(row0 + rank) * box_dim + d] = bx[d];
+        scores[row0 + rank] = sc;
+        labels[row0 + rank] = label;
+    }
+    if (tid >= (int)total && tid < K) {                          // rows behind the count hold zeros, not what an earlier call left
+        for (int d = 0; d < box_dim; ++d) boxes[(row0 + tid) * box_dim + d] = 0.f;
+        scores[row0 + tid] = 0.f;
+        labels[row0 + tid] = 0;
+    }
+    if (tid == 0) counts[g] = (int32_t)total;
 }
 
 inline size_t nms_words(int n_max) { return (size_t)((n_max + 63) / 64); }

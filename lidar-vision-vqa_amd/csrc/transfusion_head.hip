@@ -18,6 +18,9 @@
 //   k_tf_compact       decode_bbox's masks (433-451): the kept rows of a scene in proposal order.  A launch of its own because the
 //                      rank of a row is a prefix over the scene's P rows, which k_tf_tail spreads over P / 8 workgroups.
 //
+// The grid's geometry (CenterGeom), the range-and-threshold mask (box_stays, with the threshold always applied) and the compaction
+// (compact_store) are head_common.h's, shared with center_head.hip; the box arithmetic is this head's own (the sine comes first in rot).
+//
 // Order of the proposals: the fp32 heat, descending, equal values towards the LOWER flat index class * H * W + cell (the reference's
 // argsort leaves ties open); NaN first (head_common.h: key_of).  A NaN heat stays NaN whatever its neighbours (NaN * 0 in the reference),
 // and a cell with a NaN neighbour is suppressed (max_pool2d hands the NaN on, and nothing equals it).
@@ -157,8 +160,6 @@ struct TailW {
     int ffn, nb, n_cls, c_total, c_box;
     float eps;
 };
-struct TailGeom { float stride, vx, vy, rx, ry, lim[6], thresh; };
-
 __device__ __forceinline__ int branch_of(int o, int c_box, int nb) {
     if (o >= c_box) return nb - 1;
     return o < 2 ? 0 : o < 3 ? 1 : o < 6 ? 2 : o < 8 ? 3 : 4;
@@ -182,7 +183,7 @@ __device__ __forceinline__ void dot_rows(const float *__restrict__ wrow, const f
 
 __global__ __launch_bounds__(TAIL_THREADS) void k_tf_tail(const float *__restrict__ x, const float *__restrict__ qpos,
                                                            const int32_t *__restrict__ qlabels, const float *__restrict__ prop_score, int R,
-                                                           int P, TailW tw, TailGeom gm, int box_dim, float *__restrict__ raw,
+                                                           int P, TailW tw, CenterGeom gm, int box_dim, float *__restrict__ raw,
                                                            float *__restrict__ tmp_boxes, float *__restrict__ tmp_scores,
                                                            int32_t *__restrict__ tmp_keep) {
     __shared__ float xs[TAIL_ROWS][TF_D];
@@ -278,8 +279,7 @@ __global__ __launch_bounds__(TAIL_THREADS) void k_tf_tail(const float *__restric
         bx[6] = atan2f(rr[6], rr[7]);                                          // rot[:, 0] is the SINE here (transfusion_head.py:410-411)
         bx[7] = bx[8] = 0.f;
         if (box_dim == 9) { bx[7] = rr[8]; bx[8] = rr[9]; }
-        const bool keep = sc > gm.thresh && bx[0] >= gm.lim[0] && bx[1] >= gm.lim[1] && bx[2] >= gm.lim[2] && bx[0] <= gm.lim[3] &&
-                          bx[1] <= gm.lim[4] && bx[2] <= gm.lim[5];
+        const bool keep = box_stays<false>(bx, sc, gm);                        // the threshold always counts here
         for (int d = 0; d < box_dim; ++d) tmp_boxes[(int64_t)row * box_dim + d] = bx[d];
         tmp_scores[row] = sc;
         tmp_keep[row] = keep ? 1 : 0;
@@ -292,25 +292,18 @@ __global__ __launch_bounds__(MAX_P) void k_tf_compact(const float *__restrict__ 
                                                        int box_dim, float *__restrict__ boxes, float *__restrict__ scores,
                                                        int32_t *__restrict__ labels, int32_t *__restrict__ counts) {
     __shared__ uint32_t wcnt[MAX_P / 64];
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t row0 = (int64_t)b * P;
-    const bool keep = tid < P && tmp_keep[row0 + tid] != 0;
-    const uint64_t bal = __ballot(keep);
-    if (lane == 0) wcnt[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t rank = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull)), total = 0;
-    for (int q = 0; q < MAX_P / 64; ++q) { const uint32_t c = wcnt[q]; total += c; if (q < wave) rank += c; }
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t row = (int64_t)b * P + tid;
+    const bool keep = tid < P && tmp_keep[row] != 0;
+    float bx[9];
+    float sc = 0.f;
+    int label = 0;
     if (keep) {
-        for (int d = 0; d < box_dim; ++d) boxes[(row0 + rank) * box_dim + d] = tmp_boxes[(row0 + tid) * box_dim + d];
-        scores[row0 + rank] = tmp_scores[row0 + tid];
-        labels[row0 + rank] = qlabels[row0 + tid] + 1;                        // get_bboxes: .int() + 1
+        for (int d = 0; d < box_dim; ++d) bx[d] = tmp_boxes[row * box_dim + d];
+        sc = tmp_scores[row];
+        label = qlabels[row] + 1;                                              // get_bboxes: .int() + 1
     }
-    if (tid >= (int)total && tid < P) {
-        for (int d = 0; d < box_dim; ++d) boxes[(row0 + tid) * box_dim + d] = 0.f;
-        scores[row0 + tid] = 0.f;
-        labels[row0 + tid] = 0;
-    }
-    if (tid == 0) counts[b] = (int32_t)total;
+    compact_store<MAX_P>(wcnt, keep, bx, sc, label, b, P, box_dim, boxes, scores, labels, counts);
 }
 
 template <typename A>
@@ -438,10 +431,7 @@ extern "C" int lvq_transfusion_tail(const float *x, const float *query_pos, cons
     tw.w1 = w1; tw.b1 = b1; tw.w2 = w2; tw.b2 = b2; tw.gamma = gamma; tw.beta = beta;
     tw.hw1 = head_w1; tw.hscale = head_scale; tw.hshift = head_shift; tw.hw2 = head_w2; tw.hb2 = head_b2;
     tw.ffn = ffn; tw.nb = has_vel ? 6 : 5; tw.n_cls = n_cls; tw.c_box = has_vel ? 10 : 8; tw.c_total = tw.c_box + n_cls; tw.eps = eps;
-    TailGeom gm;
-    gm.stride = (float)stride; gm.vx = voxel_xy[0]; gm.vy = voxel_xy[1]; gm.rx = range_xy[0]; gm.ry = range_xy[1];
-    for (int i = 0; i < 6; ++i) gm.lim[i] = limit_range[i];
-    gm.thresh = score_thresh;
+    const CenterGeom gm = center_geom(stride, voxel_xy, range_xy, limit_range, score_thresh);
     hipStream_t st = lvq_s(stream);
     hipLaunchKernelGGL(k_tf_tail, dim3((unsigned)lvq_cdiv(R, TAIL_ROWS)), dim3(TAIL_THREADS), 0, st, x, query_pos, query_labels, prop_score, R,
                        n_proposals, tw, gm, box_dim, raw, tb, tsc, tk);

@@ -29,6 +29,9 @@ channels per task; input channels <= 512; MAX_OBJ_PER_SAMPLE <= 1024; NMS_TYPE n
 `precision`: "bf16x3" (default) or "bf16", as on the backbones.  LVQ_HEAD_TORCH_POST=1 routes the post-processing through the reference's
 own sequence of torch ops (two top-ks, gathers, masks per scene and task; NMS = lvq_boxes_iou_bev + a host walk): the cross-check and the
 timing comparison, not a fallback (it needs the same library).
+
+Shared with the other heads through head_common.py: guard, CenterStyleHead (class-id mappings, stubs), center_tasks, center_decode_args,
+center_post_cfg, collect_kept, class_agnostic_nms_torch.  `_Fused` here is also anchor_head's and transfusion_head's fused conv.
 """
 from __future__ import annotations
 
@@ -42,22 +45,13 @@ import torch.nn as nn
 from torch.nn.init import kaiming_normal_
 
 from . import _ffi as F
-from . import autograd_route as AG
 from . import ops
-from .backbone2d import DEFAULT_MODE, MODES, Planes, _Layer, to_planes
+from .backbone2d import Planes, _Layer, to_planes
+from .head_common import (BOX_BRANCHES, MAX_K, CenterStyleHead, _get, cached_plan, center_decode_args, center_post_cfg, center_tasks,  # noqa: F401
+                          class_agnostic_nms_torch, collect_kept, guard)
 
 SHARED_C = 64                  # SHARED_CONV_CHANNEL the fused convs are laid out for
 TASK_C = 64                    # output channels of a task's last conv (lvq_conv2d: c_out a multiple of 64)
-MAX_K = 1024
-BOX_BRANCHES = {"center": 2, "center_z": 1, "dim": 3, "rot": 2, "vel": 2}
-
-
-def _get(cfg, key, default=None):
-    if hasattr(cfg, "get"):
-        v = cfg.get(key, default)
-    else:
-        v = getattr(cfg, key, default)
-    return default if v is None else v
 
 
 class SeparateHead(nn.Module):
@@ -104,7 +98,7 @@ class _Fused(_Layer):
 
     def packed(self, split: bool):
         def build():
-            hi, lo = ops.conv2d_pack_weights(self._weight().contiguous(), self.c_out, self.c_in, 3, False, split)
+            hi, lo = ops.conv2d_pack_weights(self._weight().contiguous(), self.c_out, self.c_in, self.kernel, False, split)
             return hi.view(torch.int16), None if lo is None else lo.view(torch.int16)
         return F.derived(self._cache, ("w", split), self._params, build)
 
@@ -158,7 +152,7 @@ def _last_convs(seqs: List[nn.Sequential], block_diagonal: bool) -> _Fused:
     return _Fused(convs, c_in, TASK_C, False, weight, affine, [m.weight for m in convs] + [m.bias for m in convs])
 
 
-class CenterHead(nn.Module):
+class CenterHead(CenterStyleHead):
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range, voxel_size,
                  predict_boxes_when_training=True):
         super().__init__()
@@ -168,14 +162,7 @@ class CenterHead(nn.Module):
         self.point_cloud_range = point_cloud_range
         self.voxel_size = voxel_size
         self.feature_map_stride = _get(_get(model_cfg, "TARGET_ASSIGNER_CONFIG", {}), "FEATURE_MAP_STRIDE")
-        self.class_names = class_names
-        self.class_names_each_head = []
-        for i, cur_class_names in enumerate(model_cfg.CLASS_NAMES_EACH_HEAD):
-            self.class_names_each_head.append([x for x in cur_class_names if x in class_names])
-            mapping = torch.tensor([self.class_names.index(x) for x in cur_class_names if x in class_names], dtype=torch.int64)
-            self.register_buffer(f"class_id_mapping_{i}", mapping, persistent=False)          # follows .to(); not a state_dict key
-        total_classes = sum(len(x) for x in self.class_names_each_head)
-        assert total_classes == len(self.class_names), f"class_names_each_head={self.class_names_each_head}"
+        self._init_class_maps(model_cfg, class_names)
 
         norm_func = partial(nn.BatchNorm2d, eps=_get(model_cfg, "BN_EPS", 1e-5), momentum=_get(model_cfg, "BN_MOM", 0.1))
         use_bias = _get(model_cfg, "USE_BIAS_BEFORE_NORM", False)
@@ -195,79 +182,34 @@ class CenterHead(nn.Module):
         self.build_losses()
         self.precision: Optional[str] = None          # None -> "bf16x3"
 
-    @property
-    def class_id_mapping_each_head(self):
-        return [getattr(self, f"class_id_mapping_{i}") for i in range(len(self.class_names_each_head))]
-
-    def build_losses(self):
-        """The reference registers FocalLossCenterNet / RegLossCenterNet here; they hold no parameters, and there is no training route."""
-        self.add_module("hm_loss_func", nn.Module())
-        self.add_module("reg_loss_func", nn.Module())
-
-    def assign_targets(self, *args, **kwargs):
-        raise F.LvqError("CenterHead.assign_targets: training targets are out of scope (inference-only kernels)")
-
-    def get_loss(self, *args, **kwargs):
-        raise F.LvqError("CenterHead.get_loss: the losses are out of scope (inference-only kernels)")
-
     # ------------------------------------------------------------------------------------------------------------------------------
     def _plan(self):
-        plan = self.__dict__.get("_plan_cache")
-        if plan is not None:
-            return plan
+        return cached_plan(self, self._build_plan)
+
+    def _build_plan(self):
         cfg = self.model_cfg
         if int(cfg.SHARED_CONV_CHANNEL) != SHARED_C:
             raise F.LvqError(f"CenterHead: SHARED_CONV_CHANNEL = {cfg.SHARED_CONV_CHANNEL}; the fused head convs are laid out for {SHARED_C}")
         if self.shared_conv[0].in_channels > 512:
             raise F.LvqError(f"CenterHead: {self.shared_conv[0].in_channels} input channels; lvq_conv2d takes at most 512")
-        order = list(self.separate_head_cfg.HEAD_ORDER)
-        tasks = []
-        for i, head in enumerate(self.heads_list):
-            names = list(head.sep_head_dict)
-            for name in names:
-                if name != "hm" and name not in BOX_BRANCHES:
-                    raise F.LvqError(f"CenterHead: branch {name!r} has no kernel (an 'iou' branch with USE_IOU_TO_RECTIFY_SCORE is out of scope; "
-                                     f"the branches are {sorted(BOX_BRANCHES)} and hm)")
-                if name != "hm" and head.sep_head_dict[name]["out_channels"] != BOX_BRANCHES[name]:
-                    raise F.LvqError(f"CenterHead: branch {name!r} has {head.sep_head_dict[name]['out_channels']} channels, the decode reads {BOX_BRANCHES[name]}")
-            missing = [n for n in ("center", "center_z", "dim", "rot") if n not in names]
-            if missing:
-                raise F.LvqError(f"CenterHead: task {i} lacks the branches {missing}")
-            num_convs = {int(head.sep_head_dict[n]["num_conv"]) for n in names}
-            if len(num_convs) != 1 or not num_convs <= {1, 2}:
-                raise F.LvqError(f"CenterHead: task {i} has num_conv {sorted(int(head.sep_head_dict[n]['num_conv']) for n in names)}; the fused "
-                                 "convs take one num_conv for all branches (NUM_HM_CONV included), 1 or 2")
-            seqs = [getattr(head, n) for n in names]
-            widths = [int(head.sep_head_dict[n]["out_channels"]) for n in names]
-            if sum(widths) > TASK_C:
-                raise F.LvqError(f"CenterHead: task {i} has {sum(widths)} output channels; one task's last conv writes at most {TASK_C}")
-            offs, o = {}, 0
-            for n, wd in zip(names, widths):
-                offs[n], o = (o, wd), o + wd
-            two = num_convs == {2}
-            tasks.append(dict(first=_first_convs(seqs, 0) if two else None, last=_last_convs(seqs, two), offs=offs,
-                              n_cls=len(self.class_names_each_head[i])))
-        vel = "vel" in order
-        if any(("vel" in t["offs"]) != vel for t in tasks):
-            raise F.LvqError("CenterHead: 'vel' is in HEAD_ORDER of some tasks' branches only")
-        plan = dict(shared=_Layer(self.shared_conv[0], self.shared_conv[1], True), tasks=tasks, vel=vel,
-                    class_map=[self.class_names.index(x) for names in self.class_names_each_head for x in names])
-        self.__dict__["_plan_cache"] = plan
+        def one_num_conv(i, num_conv):
+            if len(set(num_conv)) != 1 or not set(num_conv) <= {1, 2}:
+                raise F.LvqError(f"CenterHead: task {i} has num_conv {sorted(num_conv)}; the fused convs take one num_conv for all "
+                                 "branches (NUM_HM_CONV included), 1 or 2")
+
+        plan = center_tasks("CenterHead", self.heads_list, self.class_names_each_head, TASK_C, self.separate_head_cfg.HEAD_ORDER, self.class_names,
+                            no_kernel_note="an 'iou' branch with USE_IOU_TO_RECTIFY_SCORE is out of scope; ",
+                            task_writes="one task's last conv writes", task_rule=one_num_conv)
+        for head, t in zip(self.heads_list, plan["tasks"]):
+            seqs = [getattr(head, n) for n in t["names"]]
+            two = t["num_conv"][0] == 2
+            t.update(first=_first_convs(seqs, 0) if two else None, last=_last_convs(seqs, two))
+        plan["shared"] = _Layer(self.shared_conv[0], self.shared_conv[1], True)
         return plan
 
     def _post_cfg(self):
-        post = self.model_cfg.POST_PROCESSING
-        nms = post.NMS_CONFIG
-        if nms.NMS_TYPE != "nms_gpu":
-            raise F.LvqError(f"CenterHead: NMS_TYPE {nms.NMS_TYPE!r} has no kernel (nms_gpu under class_agnostic_nms only; nms_normal_gpu, "
-                             "class_specific_nms and circle_nms are out of scope)")
-        if _get(post, "USE_IOU_TO_RECTIFY_SCORE", False):
-            raise F.LvqError("CenterHead: USE_IOU_TO_RECTIFY_SCORE needs an 'iou' branch, which is out of scope")
-        k = int(post.MAX_OBJ_PER_SAMPLE)
-        if k > MAX_K:
-            raise F.LvqError(f"CenterHead: MAX_OBJ_PER_SAMPLE = {k}; lvq_center_decode sorts at most {MAX_K} candidates")
-        return dict(k=k, thresh=_get(post, "SCORE_THRESH"), limit=[float(v) for v in post.POST_CENTER_LIMIT_RANGE],
-                    nms_thresh=float(nms.NMS_THRESH), pre=int(nms.NMS_PRE_MAXSIZE), post=int(nms.NMS_POST_MAXSIZE))
+        return center_post_cfg("CenterHead", self.model_cfg.POST_PROCESSING, "lvq_center_decode", rectifier=True,
+                               nms_note="; nms_normal_gpu, class_specific_nms and circle_nms are out of scope")
 
     def _maps(self, x: torch.Tensor, split: bool):
         """The conv stack: [B, C, H, W] fp32 -> maps [B, 64 n_tasks, H, W] fp32."""
@@ -289,18 +231,10 @@ class CenterHead(nn.Module):
 
     def forward(self, data_dict):
         x = data_dict["spatial_features_2d"]
-        if AG.wanted(self, x):
-            raise F.LvqError("CenterHead: inference-only kernels (BatchNorm folded, no target assignment, no losses); call it in eval() mode "
-                             "under torch.no_grad()")
-        mode = self.precision or DEFAULT_MODE
-        if mode not in MODES:
-            raise F.LvqError(f"CenterHead runs in {MODES}, not {mode!r}")
-        if x.dim() != 4:
-            raise F.LvqError(f"CenterHead: expected [B, C, H, W], got {tuple(x.shape)}")
-        F.require_cuda(x.contiguous(), *self.parameters())
+        split = guard(self, "BatchNorm folded, no target assignment, no losses", x)
         post = self._post_cfg()                        # refusals come before any launch
         plan = self._plan()
-        maps = self._maps(x.float().contiguous(), mode == "bf16x3")
+        maps = self._maps(x.float().contiguous(), split)
         self.forward_ret_dict["pred_dicts"] = self._pred_dicts(maps)
         batch_size = int(data_dict["batch_size"])
         if batch_size != maps.shape[0]:
@@ -318,15 +252,7 @@ class CenterHead(nn.Module):
 
     def decode_args(self, plan=None):
         """What lvq_center_decode takes besides the maps (also used by tests and tools)."""
-        plan = plan or self._plan()
-        chans = []
-        for i, t in enumerate(plan["tasks"]):
-            o = t["offs"]
-            chans.append([TASK_C * i + o[n][0] if n in o else -1 for n in ("center", "center_z", "dim", "rot", "vel", "hm")])
-        return dict(task_channels=chans, task_n_cls=[t["n_cls"] for t in plan["tasks"]], class_map=plan["class_map"],
-                    box_dim=9 if plan["vel"] else 7, stride=int(self.feature_map_stride),
-                    voxel_xy=[float(self.voxel_size[0]), float(self.voxel_size[1])],
-                    range_xy=[float(self.point_cloud_range[0]), float(self.point_cloud_range[1])])
+        return center_decode_args(self, plan or self._plan(), TASK_C)
 
     def _kernel_post(self, maps, plan, post):
         boxes, scores, labels, counts = ops.center_decode(maps, k=post["k"], limit_range=post["limit"], score_thresh=post["thresh"],
@@ -335,9 +261,7 @@ class CenterHead(nn.Module):
         b, t, k, d = boxes.shape
         keep, keep_count = ops.nms_bev(boxes.view(b * t, k, d), counts.view(-1), thresh=post["nms_thresh"], pre_max=post["pre"],
                                        post_max=post["post"], tag="center_nms")
-        out_b, out_s, out_l, _ = ops.center_collect(boxes, scores, labels, keep, keep_count, tag="center_collect")
-        totals = keep_count.view(b, t).cpu().sum(dim=1).tolist()            # THE device-to-host copy of a forward
-        return [dict(pred_boxes=out_b[s, :n], pred_scores=out_s[s, :n], pred_labels=out_l[s, :n]) for s, n in enumerate(totals)]
+        return collect_kept(boxes, scores, labels, keep, keep_count, "center_collect")      # holds THE device-to-host copy of a forward
 
     # ------------------------------------------------------------------------------------------------------------------------------
     # LVQ_HEAD_TORCH_POST=1: center_head.py:297-365 / centernet_utils.py:155-241 / model_nms_utils.py:6-25 as the reference's own torch ops
@@ -379,18 +303,7 @@ class CenterHead(nn.Module):
             for k in range(batch_size):
                 cur_boxes, cur_scores = box_preds[k, mask[k]], score[k, mask[k]]
                 cur_labels = mapping[class_ids[k, mask[k]].long()]
-                selected = []
-                if cur_scores.shape[0] > 0:                                 # class_agnostic_nms, score_thresh=None
-                    nms_scores, indices = torch.topk(cur_scores, k=min(post["pre"], cur_scores.shape[0]))
-                    order = nms_scores.sort(0, descending=True)[1]          # nms_gpu's own sort
-                    nms_boxes = cur_boxes[indices][order][:, :7].contiguous()
-                    over = (ops.boxes_iou_bev(nms_boxes, nms_boxes) > post["nms_thresh"]).cpu().numpy()
-                    kept, gone = [], over[0] & False
-                    for i in range(over.shape[0]):
-                        if not gone[i]:
-                            kept.append(i)
-                            gone[i + 1:] |= over[i, i + 1:]
-                    selected = indices[order[torch.tensor(kept[:post["post"]], dtype=torch.int64, device=dev)]]
+                selected = class_agnostic_nms_torch(cur_boxes, cur_scores, post)
                 ret[k]["pred_boxes"].append(cur_boxes[selected])
                 ret[k]["pred_scores"].append(cur_scores[selected])
                 ret[k]["pred_labels"].append(cur_labels[selected])
@@ -399,21 +312,6 @@ class CenterHead(nn.Module):
             ret[k]["pred_scores"] = torch.cat(ret[k]["pred_scores"], dim=0)
             ret[k]["pred_labels"] = torch.cat(ret[k]["pred_labels"], dim=0) + 1
         return ret
-
-    @staticmethod
-    def reorder_rois_for_refining(batch_size, pred_dicts):
-        """center_head.py:367-383, plain torch."""
-        num_max_rois = max(1, max(len(d["pred_boxes"]) for d in pred_dicts))        # at least one faked roi
-        pred_boxes = pred_dicts[0]["pred_boxes"]
-        rois = pred_boxes.new_zeros((batch_size, num_max_rois, pred_boxes.shape[-1]))
-        roi_scores = pred_boxes.new_zeros((batch_size, num_max_rois))
-        roi_labels = pred_boxes.new_zeros((batch_size, num_max_rois)).long()
-        for b in range(batch_size):
-            n = len(pred_dicts[b]["pred_boxes"])
-            rois[b, :n, :] = pred_dicts[b]["pred_boxes"]
-            roi_scores[b, :n] = pred_dicts[b]["pred_scores"]
-            roi_labels[b, :n] = pred_dicts[b]["pred_labels"]
-        return rois, roi_scores, roi_labels
 
 
 dense_heads_all = {"CenterHead": CenterHead}

@@ -711,6 +711,33 @@ def _ws_query(fn, what: str, *args) -> int:
     return n.value
 
 
+def _ws_or_none(query, dev, tag: str):
+    """(pointer, bytes) of the workspace query(bytes_out) asks for; a refused query gives none, so that the call itself names the reason."""
+    n = ctypes.c_size_t(0)
+    if query(ctypes.byref(n)) != F.LVQ_OK:
+        return F.ptr(None), 0
+    ws = F.workspace(n.value, dev, tag)
+    return F.ptr(ws), ws.numel()
+
+
+def _decode_tables(what: str, dev, b: int, task_channels, task_n_cls, class_map, k: int, box_dim: int, stride: int, voxel_xy, range_xy,
+                   limit_range, score_thresh: Optional[float], positive: bool = False):
+    """center_decode's and voxel_decode's host tables checked -> (the four outputs, the ABI's arguments from n_tasks to counts)."""
+    n_tasks = len(task_n_cls)
+    if len(task_channels) != n_tasks or any(len(r) != 6 for r in task_channels) or len(class_map) != sum(int(c) for c in task_n_cls):
+        raise F.LvqError(f"{what}: task_channels is [n_tasks][6], class_map holds sum(task_n_cls) entries")
+    if positive and (b <= 0 or k <= 0):
+        raise F.LvqError(f"{what}: batch = {b}, k = {k}")
+    boxes = torch.empty((b, n_tasks, k, box_dim), dtype=torch.float32, device=dev)
+    scores = torch.empty((b, n_tasks, k), dtype=torch.float32, device=dev)
+    labels = torch.empty((b, n_tasks, k), dtype=torch.int32, device=dev)
+    counts = torch.empty((b, n_tasks), dtype=torch.int32, device=dev)
+    args = (n_tasks, F.i32x([c for row in task_channels for c in row]), F.i32x(task_n_cls), F.i32x(class_map), k, box_dim, stride,
+            F.f32x(voxel_xy), F.f32x(range_xy), F.f32x(limit_range), -1.0 if score_thresh is None else float(score_thresh), F.ptr(boxes),
+            F.ptr(scores), F.ptr(labels), F.ptr(counts))
+    return (boxes, scores, labels, counts), args
+
+
 def center_decode(maps: torch.Tensor, task_channels, task_n_cls, class_map, *, k: int, box_dim: int, stride: int, voxel_xy, range_xy,
                   limit_range, score_thresh: Optional[float], tag: Optional[str] = None):
     """lvq_center_decode.  maps [B, c_total, H, W] fp32; task_channels: per task the first channel of (center, center_z, dim, rot, vel or
@@ -721,25 +748,15 @@ def center_decode(maps: torch.Tensor, task_channels, task_n_cls, class_map, *, k
     if maps.dim() != 4 or maps.dtype != torch.float32:
         raise F.LvqError(f"center_decode: expected fp32 [B, C, H, W] maps, got {maps.dtype} {tuple(maps.shape)}")
     b, c_total, h, w = maps.shape
-    n_tasks, dev = len(task_n_cls), maps.device
-    if len(task_channels) != n_tasks or any(len(r) != 6 for r in task_channels) or len(class_map) != sum(int(c) for c in task_n_cls):
-        raise F.LvqError("center_decode: task_channels is [n_tasks][6], class_map holds sum(task_n_cls) entries")
-    L = F.lib()
-    boxes = torch.empty((b, n_tasks, k, box_dim), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, n_tasks, k), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n_tasks, k), dtype=torch.int32, device=dev)
-    counts = torch.empty((b, n_tasks), dtype=torch.int32, device=dev)
-    chans = F.i32x([c for row in task_channels for c in row])
-    args = (F.ptr(maps), b, c_total, h, w, n_tasks, chans, F.i32x(task_n_cls), F.i32x(class_map), k, box_dim, stride, F.f32x(voxel_xy),
-            F.f32x(range_xy), F.f32x(limit_range), -1.0 if score_thresh is None else float(score_thresh), F.ptr(boxes), F.ptr(scores),
-            F.ptr(labels), F.ptr(counts))
-    n = ctypes.c_size_t(0)
-    rc = L.lvq_center_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), h, w, ctypes.byref(n))
-    ws = F.workspace(n.value, dev, "center_head") if rc == F.LVQ_OK else None        # a refused query: the call below names the reason
+    dev, L = maps.device, F.lib()
+    out, args = _decode_tables("center_decode", dev, b, task_channels, task_n_cls, class_map, k, box_dim, stride, voxel_xy, range_xy,
+                               limit_range, score_thresh)
+    n_tasks = len(task_n_cls)
+    ws = _ws_or_none(lambda n: L.lvq_center_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), h, w, n), dev, "center_head")
     with region(tag, dev):
-        rc = L.lvq_center_decode(*args, F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+        rc = L.lvq_center_decode(F.ptr(maps), b, c_total, h, w, *args, *ws, F.stream_ptr(dev))
     F.check(rc, f"lvq_center_decode (B={b}, {n_tasks} tasks, {h} x {w}, K={k})")
-    return boxes, scores, labels, counts
+    return out
 
 
 def boxes_iou_bev(boxes_a: torch.Tensor, boxes_b: torch.Tensor) -> torch.Tensor:
@@ -755,23 +772,28 @@ def boxes_iou_bev(boxes_a: torch.Tensor, boxes_b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _nms(fn, ws_fn, what: str, ws_tag: str, boxes: torch.Tensor, counts: torch.Tensor, thresh: float, pre_max: int, post_max: int, tag):
+    """The entry point `fn` (lvq_nms_bev / lvq_nms_bev_wide) and its workspace query `ws_fn` behind nms_bev / nms_bev_wide (`what`)."""
+    F.require_cuda(boxes, counts)
+    if boxes.dim() != 3 or boxes.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != boxes.shape[0]:
+        raise F.LvqError(f"{what}: expected fp32 boxes [G, N, >= 7] and int32 counts [G], got {tuple(boxes.shape)} and {tuple(counts.shape)}")
+    g, n_max, stride = boxes.shape
+    dev = boxes.device
+    keep = torch.empty((g, post_max), dtype=torch.int32, device=dev)
+    keep_count = torch.empty((g,), dtype=torch.int32, device=dev)
+    ws = F.workspace(_ws_query(ws_fn, f"{ws_fn.__name__} ({g} groups of {n_max})", g, n_max), dev, ws_tag)
+    with region(tag, dev):
+        rc = fn(F.ptr(boxes), stride, F.ptr(counts), g, n_max, int(pre_max), int(post_max), float(thresh), F.ptr(keep), F.ptr(keep_count),
+                F.ptr(ws), ws.numel(), F.stream_ptr(dev))
+    F.check(rc, f"{fn.__name__} ({g} groups of {n_max})")
+    return keep, keep_count
+
+
 def nms_bev(boxes: torch.Tensor, counts: torch.Tensor, *, thresh: float, pre_max: int, post_max: int, tag: Optional[str] = None):
     """lvq_nms_bev.  boxes [G, N_max, >= 7] fp32, each group in descending score order; counts [G] int32 on the device.
     Returns (keep [G, post_max] int32: kept row numbers ascending, -1 behind the count; keep_count [G] int32).  No host read."""
-    F.require_cuda(boxes, counts)
-    if boxes.dim() != 3 or boxes.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != boxes.shape[0]:
-        raise F.LvqError(f"nms_bev: expected fp32 boxes [G, N, >= 7] and int32 counts [G], got {tuple(boxes.shape)} and {tuple(counts.shape)}")
-    g, n_max, stride = boxes.shape
-    dev, L = boxes.device, F.lib()
-    keep = torch.empty((g, post_max), dtype=torch.int32, device=dev)
-    keep_count = torch.empty((g,), dtype=torch.int32, device=dev)
-    ws = F.workspace(_ws_query(L.lvq_nms_bev_workspace_bytes, f"lvq_nms_bev_workspace_bytes ({g} groups of {n_max})", g, n_max), dev,
-                     "center_head_nms")
-    with region(tag, dev):
-        rc = L.lvq_nms_bev(F.ptr(boxes), stride, F.ptr(counts), g, n_max, int(pre_max), int(post_max), float(thresh), F.ptr(keep),
-                           F.ptr(keep_count), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
-    F.check(rc, f"lvq_nms_bev ({g} groups of {n_max})")
-    return keep, keep_count
+    L = F.lib()
+    return _nms(L.lvq_nms_bev, L.lvq_nms_bev_workspace_bytes, "nms_bev", "center_head_nms", boxes, counts, thresh, pre_max, post_max, tag)
 
 
 def center_collect(boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor, keep: torch.Tensor, keep_count: torch.Tensor,
@@ -832,27 +854,14 @@ def voxel_decode(head: torch.Tensor, indices: torch.Tensor, batch: int, task_cha
         raise F.LvqError(f"voxel_decode: expected fp32 [C, N] head and int32 [N, 3] indices, got {head.dtype} {tuple(head.shape)} and "
                          f"{indices.dtype} {tuple(indices.shape)}")
     c_total, n = head.shape
-    n_tasks, dev, b = len(task_n_cls), head.device, int(batch)
-    if len(task_channels) != n_tasks or any(len(r) != 6 for r in task_channels) or len(class_map) != sum(int(c) for c in task_n_cls):
-        raise F.LvqError("voxel_decode: task_channels is [n_tasks][6], class_map holds sum(task_n_cls) entries")
-    if b <= 0 or k <= 0:
-        raise F.LvqError(f"voxel_decode: batch = {b}, k = {k}")
-    L = F.lib()
-    boxes = torch.empty((b, n_tasks, k, box_dim), dtype=torch.float32, device=dev)
-    scores = torch.empty((b, n_tasks, k), dtype=torch.float32, device=dev)
-    labels = torch.empty((b, n_tasks, k), dtype=torch.int32, device=dev)
-    counts = torch.empty((b, n_tasks), dtype=torch.int32, device=dev)
-    chans = F.i32x([c for row in task_channels for c in row])
-    args = (F.ptr(head), F.ptr(indices), n, b, c_total, n_tasks, chans, F.i32x(task_n_cls), F.i32x(class_map), k, box_dim, stride,
-            F.f32x(voxel_xy), F.f32x(range_xy), F.f32x(limit_range), -1.0 if score_thresh is None else float(score_thresh), F.ptr(boxes),
-            F.ptr(scores), F.ptr(labels), F.ptr(counts))
-    nb = ctypes.c_size_t(0)
-    rc = L.lvq_voxel_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), n, ctypes.byref(nb))
-    ws = F.workspace(nb.value, dev, "center_head") if rc == F.LVQ_OK else None       # a refused query: the call below names the reason
+    n_tasks, dev, b, L = len(task_n_cls), head.device, int(batch), F.lib()
+    out, args = _decode_tables("voxel_decode", dev, b, task_channels, task_n_cls, class_map, k, box_dim, stride, voxel_xy, range_xy,
+                               limit_range, score_thresh, positive=True)
+    ws = _ws_or_none(lambda nb: L.lvq_voxel_decode_workspace_bytes(b, n_tasks, max(int(c) for c in task_n_cls), n, nb), dev, "center_head")
     with region(tag, dev):
-        rc = L.lvq_voxel_decode(*args, F.ptr(ws), ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+        rc = L.lvq_voxel_decode(F.ptr(head), F.ptr(indices), n, b, c_total, *args, *ws, F.stream_ptr(dev))
     F.check(rc, f"lvq_voxel_decode (B={b}, {n_tasks} tasks, {n} rows, K={k})")
-    return boxes, scores, labels, counts
+    return out
 
 
 def anchor_decode(maps: torch.Tensor, anchors: torch.Tensor, *, n_anchors: int, n_cls: int, cls_channel: int, box_channel: int,
@@ -909,14 +918,12 @@ def anchor_select(scores: torch.Tensor, labels: torch.Tensor, box_preds: torch.T
     sel_labels = torch.empty((b, rows), dtype=torch.int32, device=dev)
     sel_index = torch.empty((b, rows), dtype=torch.int32, device=dev)
     sel_count = torch.empty((b,), dtype=torch.int32, device=dev)
-    nb = ctypes.c_size_t(0)
-    rc = L.lvq_anchor_select_workspace_bytes(b, n, ctypes.byref(nb))
-    ws = F.workspace(nb.value, dev, "anchor_head") if rc == F.LVQ_OK else None       # a refused query: the call below names the reason
+    ws = _ws_or_none(lambda nb: L.lvq_anchor_select_workspace_bytes(b, n, nb), dev, "anchor_head")
     with region(tag, dev):
         rc = L.lvq_anchor_select(F.ptr(scores), F.ptr(labels), F.ptr(box_preds), b, n, int(score_thresh is not None),
                                  0.0 if score_thresh is None else float(score_thresh), pre_max, F.ptr(cand), F.ptr(cand_count),
-                                 F.ptr(sel_boxes), F.ptr(sel_scores), F.ptr(sel_labels), F.ptr(sel_index), F.ptr(sel_count), F.ptr(ws),
-                                 ws.numel() if ws is not None else 0, F.stream_ptr(dev))
+                                 F.ptr(sel_boxes), F.ptr(sel_scores), F.ptr(sel_labels), F.ptr(sel_index), F.ptr(sel_count), *ws,
+                                 F.stream_ptr(dev))
     F.check(rc, f"lvq_anchor_select (B={b}, N={n}, pre_max={pre_max})")
     return sel_boxes, sel_scores, sel_labels, sel_index, sel_count
 
@@ -924,20 +931,9 @@ def anchor_select(scores: torch.Tensor, labels: torch.Tensor, box_preds: torch.T
 def nms_bev_wide(boxes: torch.Tensor, counts: torch.Tensor, *, thresh: float, pre_max: int, post_max: int, tag: Optional[str] = None):
     """lvq_nms_bev_wide: nms_bev for groups of up to 4096 rows.  boxes [G, N_max, >= 7] fp32, each group in descending score order;
     counts [G] int32 on the device.  Returns (keep [G, post_max] int32, keep_count [G] int32).  No host read."""
-    F.require_cuda(boxes, counts)
-    if boxes.dim() != 3 or boxes.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != boxes.shape[0]:
-        raise F.LvqError(f"nms_bev_wide: expected fp32 boxes [G, N, >= 7] and int32 counts [G], got {tuple(boxes.shape)} and {tuple(counts.shape)}")
-    g, n_max, stride = boxes.shape
-    dev, L = boxes.device, F.lib()
-    keep = torch.empty((g, post_max), dtype=torch.int32, device=dev)
-    keep_count = torch.empty((g,), dtype=torch.int32, device=dev)
-    ws = F.workspace(_ws_query(L.lvq_nms_bev_wide_workspace_bytes, f"lvq_nms_bev_wide_workspace_bytes ({g} groups of {n_max})", g, n_max), dev,
-                     "anchor_head_nms")
-    with region(tag, dev):
-        rc = L.lvq_nms_bev_wide(F.ptr(boxes), stride, F.ptr(counts), g, n_max, int(pre_max), int(post_max), float(thresh), F.ptr(keep),
-                                F.ptr(keep_count), F.ptr(ws), ws.numel(), F.stream_ptr(dev))
-    F.check(rc, f"lvq_nms_bev_wide ({g} groups of {n_max})")
-    return keep, keep_count
+    L = F.lib()
+    return _nms(L.lvq_nms_bev_wide, L.lvq_nms_bev_wide_workspace_bytes, "nms_bev_wide", "anchor_head_nms", boxes, counts, thresh, pre_max, post_max,
+                tag)
 
 
 def heatmap_proposals(maps: torch.Tensor, *, first_channel: int, n_cls: int, point_class_mask: int, n_proposals: int, nms_kernel_size: int = 3,
@@ -954,13 +950,10 @@ def heatmap_proposals(maps: torch.Tensor, *, first_channel: int, n_cls: int, poi
     flat = torch.empty((b, rows), dtype=torch.int32, device=dev)
     score = torch.empty((b, rows), dtype=torch.float32, device=dev)
     qhs = torch.empty((b, max(int(n_cls), 1), rows), dtype=torch.float32, device=dev)
-    nb = ctypes.c_size_t(0)
-    rc = L.lvq_heatmap_proposals_workspace_bytes(b, int(n_cls), h, w, ctypes.byref(nb))
-    ws = F.workspace(nb.value, dev, "transfusion_head") if rc == F.LVQ_OK else None   # a refused query: the call below names the reason
+    ws = _ws_or_none(lambda nb: L.lvq_heatmap_proposals_workspace_bytes(b, int(n_cls), h, w, nb), dev, "transfusion_head")
     with region(tag, dev):
         rc = L.lvq_heatmap_proposals(F.ptr(maps), b, c_total, h, w, int(first_channel), int(n_cls), int(point_class_mask), int(nms_kernel_size),
-                                     p, F.ptr(flat), F.ptr(score), F.ptr(qhs), F.ptr(ws), ws.numel() if ws is not None else 0,
-                                     F.stream_ptr(dev))
+                                     p, F.ptr(flat), F.ptr(score), F.ptr(qhs), *ws, F.stream_ptr(dev))
     F.check(rc, f"lvq_heatmap_proposals (B={b}, {n_cls} classes, {h} x {w}, P={p}, NMS_KERNEL_SIZE={nms_kernel_size})")
     return flat, score, qhs
 
@@ -1046,14 +1039,11 @@ def transfusion_tail(x: torch.Tensor, query_pos: torch.Tensor, query_labels: tor
     scores = torch.empty((b, p), dtype=torch.float32, device=dev)
     labels = torch.empty((b, p), dtype=torch.int32, device=dev)
     counts = torch.empty((b,), dtype=torch.int32, device=dev)
-    nbytes = ctypes.c_size_t(0)
-    rc = L.lvq_transfusion_tail_workspace_bytes(b, p, box_dim, ctypes.byref(nbytes))
-    ws = F.workspace(nbytes.value, dev, "transfusion_tail") if rc == F.LVQ_OK else None   # a refused query: the call below names the reason
+    ws = _ws_or_none(lambda nb: L.lvq_transfusion_tail_workspace_bytes(b, p, box_dim, nb), dev, "transfusion_tail")
     with region(tag, dev):
         rc = L.lvq_transfusion_tail(F.ptr(x), F.ptr(query_pos), F.ptr(query_labels), F.ptr(prop_score), b, p, f, int(n_cls), int(has_vel),
                                     *[F.ptr(t) for t in ffn], *[F.ptr(t) for t in norm], float(eps), *[F.ptr(t) for t in heads], int(stride),
                                     F.f32x(voxel_xy), F.f32x(range_xy), F.f32x(limit_range), float(score_thresh), F.ptr(raw), F.ptr(boxes),
-                                    F.ptr(scores), F.ptr(labels), F.ptr(counts), F.ptr(ws), ws.numel() if ws is not None else 0,
-                                    F.stream_ptr(dev))
+                                    F.ptr(scores), F.ptr(labels), F.ptr(counts), *ws, F.stream_ptr(dev))
     F.check(rc, f"lvq_transfusion_tail (B={b}, P={p}, FFN={f}, {n_cls} classes)")
     return raw, boxes, scores, labels, counts

@@ -32,6 +32,10 @@ anything else raise LvqError naming the limit, before any launch.  `precision`: 
 `precision` (default "bf16x3").  LVQ_HEAD_TORCH_POST=1 routes the post-processing through the reference's own sequence of torch ops
 (_topk_1d with the corrected class, gather_feat_idx, masks per scene, NMS = lvq_boxes_iou_bev + a host walk): the cross-check and the
 timing baseline, not a fallback.
+
+What this head shares with CenterHead is head_common.py's: CenterStyleHead (class-id mappings, stubs, reorder_rois_for_refining),
+center_tasks (the branch tables; the owner table, br_stride and the all-tasks num_conv rule are this head's own), center_decode_args,
+center_post_cfg, collect_kept and class_agnostic_nms_torch; the preamble is inference_split (a sparse tensor is not [B, C, H, W]).
 """
 from __future__ import annotations
 
@@ -44,16 +48,16 @@ import torch.nn as nn
 from torch.nn.init import kaiming_normal_
 
 from . import _ffi as F
-from . import autograd_route as AG
 from . import dense_head as DH
 from . import ops
-from .backbone3d import DEFAULT_MODE, MODES, SparseSequential, SubMConv2d, sparse_conv_rules
+from .backbone3d import SparseSequential, SubMConv2d, sparse_conv_rules
+from .head_common import (CenterStyleHead, _get, cached_plan, center_decode_args, center_post_cfg, center_tasks, class_agnostic_nms_torch,
+                          collect_kept, inference_split)
 
 HEAD_C = 128                   # SHARED_CONV_CHANNEL lvq_sparse_head is laid out for
 TASK_C = ops.HEAD_TASK_C       # output channels of a task in the head buffer
 MAX_BR = 8
 MAX_TASKS = 16
-_get = DH._get
 
 
 class SeparateHead(nn.Module):
@@ -88,7 +92,7 @@ class SeparateHead(nn.Module):
         raise F.LvqError("SeparateHead: the branches run fused inside VoxelNeXtHead.forward (there is no torch route)")
 
 
-class VoxelNeXtHead(nn.Module):
+class VoxelNeXtHead(CenterStyleHead):
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range, voxel_size,
                  predict_boxes_when_training=False):
         super().__init__()
@@ -98,18 +102,11 @@ class VoxelNeXtHead(nn.Module):
         self.point_cloud_range = point_cloud_range
         self.voxel_size = voxel_size
         self.feature_map_stride = _get(_get(model_cfg, "TARGET_ASSIGNER_CONFIG", {}), "FEATURE_MAP_STRIDE")
-        self.class_names = class_names
-        self.class_names_each_head = []
         self.gaussian_ratio = _get(model_cfg, "GAUSSIAN_RATIO", 1)
         self.gaussian_type = _get(model_cfg, "GAUSSIAN_TYPE", ["nearst", "gt_center"])
         self.iou_branch = _get(model_cfg, "IOU_BRANCH", False)
         self.double_flip = _get(model_cfg, "DOUBLE_FLIP", False)
-        for i, cur_class_names in enumerate(model_cfg.CLASS_NAMES_EACH_HEAD):
-            self.class_names_each_head.append([x for x in cur_class_names if x in class_names])
-            mapping = torch.tensor([self.class_names.index(x) for x in cur_class_names if x in class_names], dtype=torch.int64)
-            self.register_buffer(f"class_id_mapping_{i}", mapping, persistent=False)          # follows .to(); not a state_dict key
-        total_classes = sum(len(x) for x in self.class_names_each_head)
-        assert total_classes == len(self.class_names), f"class_names_each_head={self.class_names_each_head}"
+        self._init_class_maps(model_cfg, class_names)
 
         self.kernel_size_head = int(_get(model_cfg, "KERNEL_SIZE_HEAD", 3))
         self.shared_channel = int(_get(model_cfg, "SHARED_CONV_CHANNEL", 128))
@@ -127,26 +124,11 @@ class VoxelNeXtHead(nn.Module):
         self.precision: Optional[str] = None          # None -> the input tensor's precision, else "bf16x3"
         object.__setattr__(self, "_cache", {})
 
-    @property
-    def class_id_mapping_each_head(self):
-        return [getattr(self, f"class_id_mapping_{i}") for i in range(len(self.class_names_each_head))]
-
-    def build_losses(self):
-        """The reference registers FocalLossSparse / RegLossSparse here; they hold no parameters, and there is no training route."""
-        self.add_module("hm_loss_func", nn.Module())
-        self.add_module("reg_loss_func", nn.Module())
-
-    def assign_targets(self, *args, **kwargs):
-        raise F.LvqError("VoxelNeXtHead.assign_targets: training targets are out of scope (inference-only kernels)")
-
-    def get_loss(self, *args, **kwargs):
-        raise F.LvqError("VoxelNeXtHead.get_loss: the losses are out of scope (inference-only kernels)")
-
     # ------------------------------------------------------------------------------------------------------------------------------
     def _plan(self):
-        plan = self.__dict__.get("_plan_cache")
-        if plan is not None:
-            return plan
+        return cached_plan(self, self._build_plan)
+
+    def _build_plan(self):
         if self.iou_branch:
             raise F.LvqError("VoxelNeXtHead: IOU_BRANCH (the Waymo configs: an 'iou' branch, class-specific NMS with a rectifier) has no kernel")
         if self.double_flip:
@@ -157,52 +139,22 @@ class VoxelNeXtHead(nn.Module):
             raise F.LvqError(f"VoxelNeXtHead: KERNEL_SIZE_HEAD = {self.kernel_size_head}; lvq_sparse_head takes 1 or 3")
         if len(self.heads_list) > MAX_TASKS:
             raise F.LvqError(f"VoxelNeXtHead: {len(self.heads_list)} tasks; lvq_sparse_head takes at most {MAX_TASKS}")
-        order = list(self.separate_head_cfg.HEAD_ORDER)
-        tasks, all_convs = [], set()
-        for i, head in enumerate(self.heads_list):
-            names = list(head.sep_head_dict)
-            for name in names:
-                if name != "hm" and name not in DH.BOX_BRANCHES:
-                    raise F.LvqError(f"VoxelNeXtHead: branch {name!r} has no kernel (the branches are {sorted(DH.BOX_BRANCHES)} and hm)")
-                if name != "hm" and head.sep_head_dict[name]["out_channels"] != DH.BOX_BRANCHES[name]:
-                    raise F.LvqError(f"VoxelNeXtHead: branch {name!r} has {head.sep_head_dict[name]['out_channels']} channels, the decode "
-                                     f"reads {DH.BOX_BRANCHES[name]}")
-            missing = [n for n in ("center", "center_z", "dim", "rot") if n not in names]
-            if missing:
-                raise F.LvqError(f"VoxelNeXtHead: task {i} lacks the branches {missing}")
-            if len(names) > MAX_BR:
-                raise F.LvqError(f"VoxelNeXtHead: task {i} has {len(names)} branches; lvq_sparse_head takes at most {MAX_BR}")
-            all_convs |= {int(head.sep_head_dict[n]["num_conv"]) for n in names}
-            widths = [int(head.sep_head_dict[n]["out_channels"]) for n in names]
-            if sum(widths) > TASK_C:
-                raise F.LvqError(f"VoxelNeXtHead: task {i} has {sum(widths)} output channels; a task writes at most {TASK_C}")
-            offs, owner, o = {}, [], 0
-            for j, (n, wd) in enumerate(zip(names, widths)):
-                offs[n], o = (o, wd), o + wd
-                owner += [j] * wd
-            tasks.append(dict(names=names, seqs=[getattr(head, n) for n in names], offs=offs, owner=owner + [-1] * (TASK_C - len(owner)),
-                              n_cls=len(self.class_names_each_head[i])))
-        if len(all_convs) != 1 or not all_convs <= {1, 2}:
-            raise F.LvqError(f"VoxelNeXtHead: num_conv {sorted(all_convs)}; the fused convs take one num_conv for all branches of all tasks "
-                             "(NUM_HM_CONV included), 1 or 2")
-        vel = "vel" in order
-        if any(("vel" in t["offs"]) != vel for t in tasks):
-            raise F.LvqError("VoxelNeXtHead: 'vel' is in HEAD_ORDER of some tasks' branches only")
-        plan = dict(tasks=tasks, vel=vel, num_conv=all_convs.pop(), br_stride=max(len(t["names"]) for t in tasks),
-                    class_map=[self.class_names.index(x) for names in self.class_names_each_head for x in names])
-        self.__dict__["_plan_cache"] = plan
+        def one_num_conv(tasks):
+            all_convs = {c for t in tasks for c in t["num_conv"]}
+            if len(all_convs) != 1 or not all_convs <= {1, 2}:
+                raise F.LvqError(f"VoxelNeXtHead: num_conv {sorted(all_convs)}; the fused convs take one num_conv for all branches of all "
+                                 "tasks (NUM_HM_CONV included), 1 or 2")
+
+        plan = center_tasks("VoxelNeXtHead", self.heads_list, self.class_names_each_head, TASK_C, self.separate_head_cfg.HEAD_ORDER,
+                            self.class_names, max_branches=MAX_BR, head_rule=one_num_conv)
+        for head, t in zip(self.heads_list, plan["tasks"]):
+            owner = [j for j, wd in enumerate(t["widths"]) for _ in range(wd)]
+            t.update(seqs=[getattr(head, n) for n in t["names"]], owner=owner + [-1] * (TASK_C - len(owner)))
+        plan.update(num_conv=plan["tasks"][0]["num_conv"][0], br_stride=max(len(t["names"]) for t in plan["tasks"]))
         return plan
 
     def _post_cfg(self):
-        post = self.model_cfg.POST_PROCESSING
-        nms = post.NMS_CONFIG
-        if nms.NMS_TYPE != "nms_gpu":
-            raise F.LvqError(f"VoxelNeXtHead: NMS_TYPE {nms.NMS_TYPE!r} has no kernel (nms_gpu under class_agnostic_nms only)")
-        k = int(post.MAX_OBJ_PER_SAMPLE)
-        if k > DH.MAX_K or k <= 0:
-            raise F.LvqError(f"VoxelNeXtHead: MAX_OBJ_PER_SAMPLE = {k}; lvq_voxel_decode sorts 1 .. {DH.MAX_K} candidates")
-        return dict(k=k, thresh=_get(post, "SCORE_THRESH"), limit=[float(v) for v in post.POST_CENTER_LIMIT_RANGE],
-                    nms_thresh=float(nms.NMS_THRESH), pre=int(nms.NMS_PRE_MAXSIZE), post=int(nms.NMS_POST_MAXSIZE))
+        return center_post_cfg("VoxelNeXtHead", self.model_cfg.POST_PROCESSING, "lvq_voxel_decode", positive_k=True)
 
     def _operands(self, plan, split: bool):
         """Packed first-conv weights, folded norms, last-conv weights and biases of all tasks: one entry per precision form, rebuilt when
@@ -267,26 +219,14 @@ class VoxelNeXtHead(nn.Module):
 
     def decode_args(self, plan=None):
         """What lvq_voxel_decode takes besides the head buffer and the indices (also used by tests and tools)."""
-        plan = plan or self._plan()
-        chans = []
-        for i, t in enumerate(plan["tasks"]):
-            o = t["offs"]
-            chans.append([TASK_C * i + o[n][0] if n in o else -1 for n in ("center", "center_z", "dim", "rot", "vel", "hm")])
-        return dict(task_channels=chans, task_n_cls=[t["n_cls"] for t in plan["tasks"]], class_map=plan["class_map"],
-                    box_dim=9 if plan["vel"] else 7, stride=int(self.feature_map_stride),
-                    voxel_xy=[float(self.voxel_size[0]), float(self.voxel_size[1])],
-                    range_xy=[float(self.point_cloud_range[0]), float(self.point_cloud_range[1])])
+        return center_decode_args(self, plan or self._plan(), TASK_C)
 
     def forward(self, data_dict):
         x = data_dict["encoded_spconv_tensor"]
         feats = x.features
-        if AG.wanted(self, feats):
-            raise F.LvqError("VoxelNeXtHead: inference-only kernels (BatchNorm folded, no target assignment, no losses); call it in eval() "
-                             "mode under torch.no_grad()")
-        mode = self.precision or getattr(x, "precision", None) or DEFAULT_MODE
-        if mode not in MODES:
-            raise F.LvqError(f"VoxelNeXtHead runs in {MODES}, not {mode!r}")
-        post = self._post_cfg()                        # refusals come before any launch
+        split = inference_split(self, "BatchNorm folded, no target assignment, no losses", feats,
+                                mode=self.precision or getattr(x, "precision", None))
+        post = self._post_cfg()                      # refusals come before any launch
         plan = self._plan()
         if feats.dim() != 2 or feats.shape[1] != HEAD_C or len(x.spatial_shape) != 2:
             raise F.LvqError(f"VoxelNeXtHead: expected a 2-D sparse tensor with {HEAD_C} channels, got features {tuple(feats.shape)} on "
@@ -296,7 +236,7 @@ class VoxelNeXtHead(nn.Module):
         indices = x.indices if x.indices.dtype == torch.int32 else x.indices.to(torch.int32)
         indices = indices.contiguous()
         batch_size = int(data_dict["batch_size"])
-        buf = self.head_rows(feats, indices, x.spatial_shape, int(x.batch_size), mode == "bf16x3")
+        buf = self.head_rows(feats, indices, x.spatial_shape, int(x.batch_size), split)
         self.forward_ret_dict["pred_dicts"] = self._pred_dicts(buf)
         self.forward_ret_dict["voxel_indices"] = x.indices
         self.forward_ret_dict["batch_index"] = x.indices[:, 0]
@@ -306,7 +246,7 @@ class VoxelNeXtHead(nn.Module):
             pred_dicts = self._kernel_post(buf, indices, batch_size, plan, post)
         data_dict["final_box_dicts"] = pred_dicts
         if self.predict_boxes_when_training:
-            rois, roi_scores, roi_labels = DH.CenterHead.reorder_rois_for_refining(batch_size, pred_dicts)
+            rois, roi_scores, roi_labels = self.reorder_rois_for_refining(batch_size, pred_dicts)
             data_dict["rois"], data_dict["roi_scores"], data_dict["roi_labels"] = rois, roi_scores, roi_labels
             data_dict["has_class_labels"] = True
         return data_dict
@@ -318,10 +258,8 @@ class VoxelNeXtHead(nn.Module):
         b, t, k, d = boxes.shape
         keep, keep_count = ops.nms_bev(boxes.view(b * t, k, d), counts.view(-1), thresh=post["nms_thresh"], pre_max=post["pre"],
                                        post_max=post["post"], tag="voxel_nms")
-        out_b, out_s, out_l, _ = ops.center_collect(boxes, scores, labels, keep, keep_count, tag="voxel_collect")
-        totals = keep_count.view(b, t).cpu().sum(dim=1).tolist()            # THE device-to-host copy of a forward
-        return [dict(pred_boxes=out_b[s, :n], pred_scores=out_s[s, :n], pred_labels=out_l[s, :n], pred_ious=[None] * t)
-                for s, n in enumerate(totals)]
+        kept = collect_kept(boxes, scores, labels, keep, keep_count, "voxel_collect")      # holds THE device-to-host copy of a forward
+        return [dict(d, pred_ious=[None] * t) for d in kept]
 
     # ------------------------------------------------------------------------------------------------------------------------------
     # LVQ_HEAD_TORCH_POST=1: voxelnext_head.py:418-488 / centernet_utils.py:243-354 / model_nms_utils.py:6-25 as the reference's own torch ops
@@ -362,18 +300,7 @@ class VoxelNeXtHead(nn.Module):
                     mask &= sc > post["thresh"]
                 cur_boxes, cur_scores = box_preds[mask], sc[mask]
                 cur_labels = mapping[class_ids[mask].long()]
-                selected = []
-                if cur_scores.shape[0] > 0:                                     # class_agnostic_nms, score_thresh=None
-                    nms_scores, sel = torch.topk(cur_scores, k=min(post["pre"], cur_scores.shape[0]))
-                    order = nms_scores.sort(0, descending=True)[1]              # nms_gpu's own sort
-                    nms_boxes = cur_boxes[sel][order][:, :7].contiguous()
-                    over = (ops.boxes_iou_bev(nms_boxes, nms_boxes) > post["nms_thresh"]).cpu().numpy()
-                    kept, gone = [], over[0] & False
-                    for i in range(over.shape[0]):
-                        if not gone[i]:
-                            kept.append(i)
-                            gone[i + 1:] |= over[i, i + 1:]
-                    selected = sel[order[torch.tensor(kept[:post["post"]], dtype=torch.int64, device=dev)]]
+                selected = class_agnostic_nms_torch(cur_boxes, cur_scores, post)
                 ret[k]["pred_boxes"].append(cur_boxes[selected])
                 ret[k]["pred_scores"].append(cur_scores[selected])
                 ret[k]["pred_labels"].append(cur_labels[selected])
@@ -383,8 +310,6 @@ class VoxelNeXtHead(nn.Module):
             ret[k]["pred_scores"] = torch.cat(ret[k]["pred_scores"], dim=0)
             ret[k]["pred_labels"] = torch.cat(ret[k]["pred_labels"], dim=0) + 1
         return ret
-
-    reorder_rois_for_refining = staticmethod(DH.CenterHead.reorder_rois_for_refining)
 
 
 dense_heads_all = dict(DH.dense_heads_all, VoxelNeXtHead=VoxelNeXtHead)

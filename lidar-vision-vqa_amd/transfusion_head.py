@@ -47,6 +47,9 @@ Supported: HIDDEN_CHANNEL 128; NUM_HEADS in 1, 2, 4, 8; FFN_CHANNEL a multiple o
 (NUM_HM_CONV = 2); branches center, height, dim, rot and an optional vel; NUM_PROPOSALS <= 1024; NMS_KERNEL_SIZE 3; input channels <= 512;
 <= 64 classes (nuScenes mode >= 10, Waymo mode >= 3: the reference indexes them); use_sigmoid True.  Anything else raises LvqError naming the
 limit, before any launch.  `precision`: "bf16x3" (default) or "bf16", as on the other heads; the tail's bits do not depend on it.
+
+Shared with the other heads: the forward preamble and the plan cache (head_common.guard, cached_plan), the fused convs (dense_head._Fused),
+and in the kernels the geometry, the range-and-threshold mask and the compaction of csrc/head_common.h.
 """
 from __future__ import annotations
 
@@ -63,8 +66,9 @@ from . import _ffi as F
 from . import anchor_head as AH
 from . import autograd_route as AG
 from . import ops
-from .backbone2d import DEFAULT_MODE, MODES, _Layer, to_planes
-from .dense_head import _Fused, _get
+from .backbone2d import _Layer, to_planes
+from .dense_head import _Fused
+from .head_common import _get, cached_plan, guard
 
 HIDDEN = 128
 HEAD_C = 64
@@ -266,9 +270,9 @@ class TransFusionHead(nn.Module):
 
     # ------------------------------------------------------------------------------------------------------------------------------
     def _plan(self):
-        plan = self.__dict__.get("_plan_cache")
-        if plan is not None:
-            return plan
+        return cached_plan(self, self._build_plan)
+
+    def _build_plan(self):
         cfg, dec = self.model_cfg, self.decoder
         n_cls = int(self.num_classes)
         if int(cfg.HIDDEN_CHANNEL) != HIDDEN:
@@ -323,7 +327,7 @@ class TransFusionHead(nn.Module):
             shift[:n_cls] = last.bias.detach().float()
             return torch.ones_like(shift), shift
 
-        plan = dict(
+        return dict(
             shared=_Fused([shared], shared.in_channels, HIDDEN, False, lambda: shared.weight.detach().float(),
                           lambda: (torch.ones_like(shared.bias, dtype=torch.float32), shared.bias.detach().float().contiguous()),
                           [shared.weight, shared.bias]),
@@ -331,8 +335,6 @@ class TransFusionHead(nn.Module):
             hm1=_Fused([last], HIDDEN, 64, False, last_w, last_affine, [last.weight, last.bias]),
             n_cls=n_cls, p=p, vel=vel, ffn=ffn, heads=int(cfg.NUM_HEADS), thresh=thresh, limit=limit,
             mask=sum(1 << c for c in point), branches=names, cache={})
-        self.__dict__["_plan_cache"] = plan
-        return plan
 
     def _bf_weight(self, plan, key, tensor, split):
         """A Linear weight as the bf16 (hi, lo) W operand of lvq_gemm_bf16, per weights version."""
@@ -443,20 +445,11 @@ class TransFusionHead(nn.Module):
 
     def forward(self, batch_dict):
         x = batch_dict["spatial_features_2d"]
-        if AG.wanted(self, x):
-            raise F.LvqError("TransFusionHead: inference-only kernels (BatchNorm folded, no assigner, no losses); call it in eval() mode under "
-                             "torch.no_grad()")
-        mode = self.precision or DEFAULT_MODE
-        if mode not in MODES:
-            raise F.LvqError(f"TransFusionHead runs in {MODES}, not {mode!r}")
-        if x.dim() != 4:
-            raise F.LvqError(f"TransFusionHead: expected [B, C, H, W], got {tuple(x.shape)}")
-        F.require_cuda(x.contiguous(), *self.parameters())
+        split = guard(self, "BatchNorm folded, no assigner, no losses", x)
         plan = self._plan()                            # refusals come before any launch
         b, _, h, w = x.shape
         if h < 3 or w < 3 or plan["p"] > plan["n_cls"] * h * w:
             raise F.LvqError(f"TransFusionHead: a {h} x {w} map with {plan['n_cls']} classes cannot give {plan['p']} proposals of 3 x 3 maxima")
-        split = mode == "bf16x3"
         n_cls, p = plan["n_cls"], plan["p"]
         lidar, maps = self._dense(x.float().contiguous(), plan, split)
         ret = self.forward_ret_dict
